@@ -17,16 +17,28 @@ driver's own command line: torch.distributed.run on 127.0.0.1) and exits
 non-zero if fewer than N GPUs are visible; under a launcher WORLD_SIZE must
 equal --gpus.  `n_gpus` in the line is the number of ranks that really ran.
 
-On one GPU the same JSON line carries a `configs` array: the other BASELINE
-configurations (Caesar, the NFT cat/dog scan on its own corpus, the 1000-entry
-dictionary) and the general kernel families, each with the kernels' HIP-event
-time, its fraction of the HBM roofline, a `verified` flag and the reference CPU
-binary timed on a bounded sample of the same workload.  On N > 1 GPUs it carries
-the two configurations that BASELINE.json shards: configs[3] strong-scaled (one
-corpus of --bytes cut into N line shards) and configs[4] weak-scaled (--bytes
-per GPU: 64 GiB at 8 x 8 GiB), each verified on every rank.
+A plain run does only what the headline needs: set up, warm up, time exactly
+--steps scans, write the outputs (--dump-outputs DIR) and print the line.  Its
+output is not checked ("verified": null) and it carries no CPU baseline.
 
-    python bench.py                       # 1 GPU
+With --full the headline's output is checked and the same JSON line carries the
+rest.  On one GPU: the reference CPU binary timed on a bounded sample of the
+headline workload, and a `configs` array: the other BASELINE configurations
+(Caesar, the NFT cat/dog scan on its own corpus, the 1000-entry dictionary) and
+the general kernel families, each with the kernels' HIP-event time, its fraction
+of the HBM roofline, a `verified` flag and the reference CPU binary timed on a
+bounded sample of the same workload.  On N > 1 GPUs it carries the two
+configurations that BASELINE.json shards: configs[3] strong-scaled (one corpus
+of --bytes cut into N line shards) and configs[4] weak-scaled (--bytes per GPU:
+64 GiB at 8 x 8 GiB), each verified on every rank.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's
+output buffer and its length) as DIR/*.npy, ~25 MB whatever the size: see
+dump_outputs().  The inputs are seeded, so two builds run with the same
+arguments can be compared file by file.
+
+    python bench.py                       # 1 GPU, the headline alone
+    python bench.py --full                # ... and everything else
     python bench.py --gpus 8              # starts 8 ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
 
@@ -597,6 +609,50 @@ def self_launch(n_gpus, stub):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_EDGE = 1 << 20         # bytes of the output's head and of its tail, dumped whole
+DUMP_SAMPLE = 4 << 20       # output bytes dumped at positions drawn with DUMP_SEED
+DUMP_SEED = 0x64756d70
+DUMP_BLOCK = 2 << 20        # bytes per block of the block sums
+
+
+def dump_outputs(d, out, m):
+    """--dump-outputs DIR: the output a caller of the timed path receives (the first m bytes of `out`, and m) as float .npy files
+    of ~25 MB in all, whatever m is:
+      output_length.npy      float64 [1]         m
+      output_head.npy        float32 [<= 1 Mi]   the first DUMP_EDGE bytes
+      output_tail.npy        float32 [<= 1 Mi]   the last DUMP_EDGE bytes
+      output_sample.npy      float32 [4 Mi]      the bytes at DUMP_SAMPLE positions in [0, m), drawn with DUMP_SEED and sorted
+      output_block_sums.npy  float64 [blocks, 2] per DUMP_BLOCK bytes: the sum of the bytes, and of byte * (1 + offset in block % 251)
+    Every byte of the output counts in the block sums (exact in float64: < 2^53)."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    y = out[:m]
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    pos = torch.sort(torch.randint(0, m, (DUMP_SAMPLE,), generator=g))[0] if m else torch.zeros(0, dtype=torch.int64)
+    w = (torch.arange(DUMP_BLOCK, device=y.device) % 251 + 1).to(torch.int32)
+    sums = []
+    step = 128 * DUMP_BLOCK
+    for lo in range(0, m, step):
+        x = y[lo:lo + step]
+        full = x.numel() // DUMP_BLOCK * DUMP_BLOCK
+        if full:
+            b = x[:full].view(-1, DUMP_BLOCK).to(torch.int32)
+            sums.append(torch.stack([b.sum(1, dtype=torch.int64), (b * w).sum(1, dtype=torch.int64)], 1))
+        if full < x.numel():
+            b = x[full:].to(torch.int32)
+            sums.append(torch.stack([b.sum(dtype=torch.int64), (b * w[:b.numel()]).sum(dtype=torch.int64)]).view(1, 2))
+    arrays = {
+        "output_length": np.array([m], dtype=np.float64),
+        "output_head": y[:DUMP_EDGE].cpu().numpy().astype(np.float32),
+        "output_tail": y[max(m - DUMP_EDGE, 0):].cpu().numpy().astype(np.float32),
+        "output_sample": y[pos.to(y.device)].cpu().numpy().astype(np.float32),
+        "output_block_sums": (torch.cat(sums).cpu().numpy() if sums else np.zeros((0, 2))).astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -611,9 +667,14 @@ def main():
     ap.add_argument("--cpu-sample-mib", type=int, default=256)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the configs array and the host-buffer rate")
+    ap.add_argument("--full", action="store_true", help="also check the output and measure the CPU baseline, the configs array and the "
+                                                        "host-buffer rate (without it: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output as DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     stub = os.environ.get("TRRE_BENCH_STUB") == "1"
 
     # ---- who runs: N ranks, one per GPU -------------------------------------------------------------------------------
@@ -703,10 +764,12 @@ def main():
             p.enqueue(inp, out)
         return p.finish()
 
-    # warmup + one verified pass
+    # warmup (+ one verified pass with --full)
     m = run_steps(prog, max(args.warmup, 1))
     if stub:
         verified, verify_how = True, "stub: nothing scanned"
+    elif not args.full:
+        verified, verify_how = None, "not checked in a plain run (bench.py --full checks it)"
     elif pattern == "[a:A-z:Z]":
         low = (inp >= 97) & (inp <= 122)
         verified = bool(m == n and torch.equal(out[:n], torch.where(low, inp - 32, inp)))
@@ -718,10 +781,12 @@ def main():
         tmp = None if lp else torch.empty(out.numel() // 2 + (2 << 20), dtype=torch.uint8, device=dev)
         verified, verify_how = verify_scan(prog, Oracle(pattern, engine), inp, out, m, lp, 1 << 20, tmp)
         del tmp
-    if reduce(1.0 if verified else 0.0, "min") < 1.0:
+    if verified is not None and reduce(1.0 if verified else 0.0, "min") < 1.0:
         raise SystemExit("bench: the output is wrong on some rank (rank %d: %s)" % (rank, verify_how))
 
     elapsed, m, kernel_ms = timed(prog, inp, out, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, m)             # (before the --full legs reuse `out`)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = world * n / (elapsed / args.steps) / 1e9          # whole-job input GB/s
@@ -766,14 +831,14 @@ def main():
         "verify": verify_how,
     }
 
-    extras = rank == 0 and world == 1 and not args.no_extras and not stub
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu and not stub
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and not stub
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu and not stub
     if want_cpu:
         line["cpu_baseline"] = cpu_baseline(pattern, engine, host_sample(inp, args.cpu_sample_mib << 20), os.cpu_count() or 1)
     elif rank == 0:
         line["cpu_baseline"] = None
 
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # ---- the BASELINE configurations that shard, in the N-GPU line ---------------------------------------------------
         #   configs[3]  '(cat:dog|dog:cat)' NFT over ONE corpus of --bytes, line-sharded over the ranks (strong scaling)
         #   configs[4]  the 1000-entry dictionary, --bytes per GPU (weak scaling: 64 GiB at 8 x 8 GiB)

@@ -3,7 +3,8 @@
 (oracle/_ref/trre, oracle/_ref/trre_dft — built by oracle/Makefile from the
 sources under /root/reference).  Run in the build container only:
 
-    python tests/make_golden.py
+    python tests/make_golden.py            # golden.json
+    python tests/make_golden.py --fresh    # fresh.json
 
 The file holds data only: named inputs and, per (pattern, input, engine), the
 bytes the reference printed in scan mode (or "fail" when it exited non-zero /
@@ -227,5 +228,30 @@ def main():
              os.path.getsize(path)))
 
 
+def fresh():
+    """tests/golden/fresh.json: per golden_lib.FRESH input, its digest and the digest of the reference's scan-mode output for
+    every (pattern, engine) of its cases"""
+    import golden_lib
+    build_oracle()
+    doc = {"about": "length and SHA-256 of scan-mode outputs of the compiled reference (c0stya/trre @ 2025-05-23) on the seeded "
+                    "inputs of golden_lib.FRESH, see make_golden.py"}
+    with tempfile.TemporaryDirectory() as td:
+        for name, (_, _, cases) in golden_lib.FRESH.items():
+            data = golden_lib.fresh_input(name)
+            path = os.path.join(td, name)
+            with open(path, "wb") as f:
+                f.write(data)
+            out = []
+            for pat, eng in cases:
+                rc, got, err = run_ref_full(eng, pat, path)
+                assert rc == 0, (name, pat, eng, rc, err)
+                out.append({"pattern": pat, "engine": eng, "output": golden_lib.digest(got)})
+            doc[name] = {"input": golden_lib.digest(data), "cases": out}
+    path = os.path.join(HERE, "golden", "fresh.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+    print("wrote %s: %d outputs" % (path, sum(len(v["cases"]) for k, v in doc.items() if k != "about")))
+
+
 if __name__ == "__main__":
-    main()
+    fresh() if sys.argv[1:] == ["--fresh"] else main()

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -21,7 +23,7 @@ def run(args, env=None, timeout=600):
 
 
 def test_gpus_flag_starts_that_many_ranks():
-    r = run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--bytes", str(1 << 20)], {"TRRE_BENCH_STUB": "1"})
+    r = run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--bytes", str(1 << 20), "--full"], {"TRRE_BENCH_STUB": "1"})
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout.decode()                  # rank 0 alone prints
@@ -82,3 +84,66 @@ def test_gpus_flag_fails_loudly_without_the_devices():
 def test_world_size_must_match_the_flag():
     r = run(["--gpus", "2", "--steps", "1"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "TRRE_BENCH_STUB": "1"})
     assert r.returncode != 0 and b"WORLD_SIZE=1" in r.stderr
+
+
+def _dumped(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_a_plain_run_times_the_headline_alone_and_dumps_its_output(tmp_path):
+    """without --full: EXACTLY --steps timed scans (the stub sleeps 2 ms in each), no configs, no CPU baseline, no check; with
+    --dump-outputs the last step's output as float .npy files under 64 MB — the same files from run to run"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        r = run(["--gpus", "1", "--steps", "5", "--warmup", "1", "--bytes", str(1 << 20), "--dump-outputs", d], {"TRRE_BENCH_STUB": "1"})
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        line = json.loads(r.stdout.decode().rstrip("\n").splitlines()[-1])
+        assert line["steps"] == 5 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["ms_per_step"] >= 2.0
+        for k2 in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert line[k2] is not None, k2
+        assert "configs" not in line and line["cpu_baseline"] is None
+        dumps.append(_dumped(d))
+    a, b = dumps
+    assert sorted(a) == ["output_block_sums", "output_head", "output_length", "output_sample", "output_tail"]
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    assert a["output_length"][0] == 1 << 20                     # (the stub's output is its input)
+    head = a["output_head"].astype(np.int64)
+    assert a["output_block_sums"].shape == (1, 2) and a["output_block_sums"][0, 0] == head.sum()
+    assert a["output_block_sums"][0, 1] == (head * (np.arange(head.size) % 251 + 1)).sum()
+
+
+def test_a_plain_run_on_n_ranks_leaves_the_sharded_configs_to_full():
+    """the configurations that shard ride along with --full only (test_gpus_flag_starts_that_many_ranks)"""
+    r = run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--bytes", str(1 << 20)], {"TRRE_BENCH_STUB": "1"})
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert "configs" not in json.loads(r.stdout.decode().rstrip("\n").splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_what_the_scan_computed(tmp_path):
+    """on the device: the dump of a plain run equals the dump of an independent torch byte map of the same seeded input"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import bench
+    import corpora
+    n = 64 << 20
+    d = str(tmp_path / "bench")
+    r = run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--bytes", str(n), "--dump-outputs", d])
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads(r.stdout.decode().rstrip("\n").splitlines()[-1])
+    assert line["steps"] == 3 and line["config"]["output_bytes_per_gpu"] == n and line["ms_per_step"] > 0
+    x = corpora.printable_lines(n, corpora.SEED0 + 2, torch.device("cuda", 0))
+    want = torch.where((x >= 97) & (x <= 122), x - 32, x)
+    bench.dump_outputs(str(tmp_path / "want"), want, n)
+    got, exp = _dumped(d), _dumped(str(tmp_path / "want"))
+    assert sorted(got) == sorted(exp)
+    for name in exp:
+        assert np.array_equal(got[name], exp[name]), name

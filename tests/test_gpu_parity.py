@@ -333,13 +333,14 @@ def test_capacity_error_reports_needed_size():
     assert rc == trre_amd.api.E_CAPACITY and m.value == len(Oracle("a:xyz", "dft").scan(data))
 
 
-@pytest.mark.skipif(not ref_available(), reason="compiled reference (oracle/_ref) did not travel")
 def test_against_the_compiled_reference_binary():
-    rng = random.Random(21)
-    data = corpus.word_soup(rng, 2 << 20) + corpus.printable_lines(rng, 2 << 20)
-    for pat, eng in [("[a:A-z:Z]", "dft"), ("[a:b-y:zz:a]", "dft"), ("(cat:dog|dog:cat)", "nft"),
-                     ("(cat:dog|dog:cat)", "dft"), ("cat:dog", "nft")]:
-        assert gpu_scan(prog(pat, eng), data) == ref_scan(pat, eng, data, timeout=600), (pat, eng)
+    """4 MiB of seeded text against the digests of the compiled reference's outputs (tests/golden/fresh.json), and against the
+    binary itself when oracle/_ref travelled along"""
+    for pat, eng, data, want in golden_lib.fresh_cases("gpu"):
+        got = gpu_scan(prog(pat, eng), data)
+        assert golden_lib.digest(got) == want, (pat, eng)
+        if ref_available():
+            assert got == ref_scan(pat, eng, data, timeout=600), (pat, eng)
 
 
 def test_full_size_properties_1gib_uppercase():

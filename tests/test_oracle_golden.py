@@ -66,14 +66,14 @@ def test_line_sharded_threads_equal_single_thread():
         assert scan_mt(pat, eng, 4, data) == Oracle(pat, eng).scan(data)
 
 
-@pytest.mark.skipif(not ref_available(), reason="compiled reference (oracle/_ref) not present")
 def test_oracle_equals_compiled_reference_on_fresh_inputs():
-    import random
-    rng = random.Random(11)
-    data = corpus.word_soup(rng, 30000) + corpus.printable_lines(rng, 30000)
-    for pat in corpus.CONFIG_PATTERNS + ["a:xyz", "[aie]:", "abc:2|ab:1"]:
-        for eng in ("nft", "dft"):
-            assert Oracle(pat, eng).scan(data) == ref_scan(pat, eng, data), (pat, eng)
+    """60 kB of seeded text against the digests of the compiled reference's outputs (tests/golden/fresh.json), and against the
+    binary itself where oracle/_ref was built"""
+    for pat, eng, data, want in golden_lib.fresh_cases("oracle"):
+        got = Oracle(pat, eng).scan(data)
+        assert golden_lib.digest(got) == want, (pat, eng)
+        if ref_available():
+            assert got == ref_scan(pat, eng, data), (pat, eng)
 
 
 def test_inverted_bounds_are_the_lower_bound_only():
