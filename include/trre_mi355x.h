@@ -85,9 +85,9 @@ extern "C" {
 #define TRRE_KERNEL_BYTEMAP 1   /* memoryless tables: streaming byte map */
 #define TRRE_KERNEL_TILE_LP 2   /* length-preserving tables: one lane per line, single launch */
 #define TRRE_KERNEL_TILE_GEN 3  /* any tables: count + scan + emit */
-#define TRRE_KERNEL_STREAM_LP 4 /* scan loop folded into the tables, length-preserving: in-place, single launch */
+#define TRRE_KERNEL_STREAM_LP 4 /* scan loop folded into the tables, length-preserving: output at the input's positions, single launch */
 #define TRRE_KERNEL_STREAM_GEN 5 /* scan loop folded into the tables, any output length: count + scan + emit */
-#define TRRE_KERNEL_GUIDED_LP 6  /* NFT engine, any pattern (round 4: DFT engine too, any pattern that is not a byte map): backward DFA sweep (one symbol per byte) + guided forward transducer, in place */
+#define TRRE_KERNEL_GUIDED_LP 6  /* NFT engine, any pattern (round 4: DFT engine too, any pattern that is not a byte map): backward DFA sweep (one symbol per byte) + guided forward transducer, output at the input's positions */
 #define TRRE_KERNEL_GUIDED_GEN 7 /* the same, any output length: backward sweep, count + scan + emit */
 
 #define TRRE_KERNEL_GENERATE 8    /* generator modes: backward viability sweep and enumeration (count, exclusive sum, emit) on the device;
@@ -149,7 +149,14 @@ size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_
  *   stream     : hipStream_t (NULL = default stream)
  * Semantics, byte for byte: output = concat over getline() records of
  * scan_line(record minus its last byte, cut at the first NUL) + "\n".
- * Synchronous with respect to `stream` on return. */
+ * Synchronous with respect to `stream` on return.
+ * Aliasing: d_in == d_out (a scan in place) is valid for every family and mode, with any cap that holds the
+ * output, and gives byte for byte what separate buffers give (the scan reads a device copy of the input:
+ * n more bytes of device memory and one device-to-device copy per call).  Any other overlap of
+ * [d_in, d_in + n) and [d_out, d_out + cap) returns TRRE_E_ARG before the device is touched: nothing is
+ * launched or written.  In place, TRRE_E_CAPACITY leaves the first n bytes holding the input, so the size
+ * query and a retry from the same buffer work; TRRE_E_DIVERGES leaves the reference's partial output and
+ * *out_len its length, as with separate buffers. */
 int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, size_t* out_len,
                      void* stream);
 
@@ -163,11 +170,13 @@ uint32_t trre_last_scan_flags(void);
 /* Split form for back-to-back launches: enqueue only (no host sync), then collect status/size once.
  * One scan may be in flight per (prog, device); enqueues repeated before the finish must be the same
  * scan (same buffers, size and stream: a benchmark loop) — anything else returns TRRE_E_ARG.  The split
- * form uses the calling thread's current device and is not serialised against other threads. */
+ * form uses the calling thread's current device and is not serialised against other threads.
+ * Aliasing as for trre_scan_device.  Repeated enqueues of the same scan in place all read the input as
+ * it was at the first enqueue of the batch (its copy), not what an earlier launch wrote over it. */
 int trre_scan_enqueue(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, void* stream);
 int trre_scan_finish(trre_prog* p, size_t* out_len);
 
-/* Host buffers on `device`: what the scan branch of the reference's main() does with a FILE* (the
+/* Host buffers on `device` (in and out must not overlap at all, out == in included: TRRE_E_ARG): what the scan branch of the reference's main() does with a FILE* (the
  * getline loop of trre_nft.c:776-790 / trre_dft.c:1272-1286).  The input goes through in 64 MiB chunks
  * cut at line ends, three in flight on their own streams (staging copy, H2D, scan, D2H and the copy out
  * overlap); records are independent, so the chunks' outputs concatenate to exactly the output of one scan.
@@ -184,6 +193,7 @@ int trre_scan_host(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size
  * Threading: a compiled program may be used from several host threads at once; calls that target the same
  * device are serialised per (prog, device), calls on different devices run in parallel.  Compilation
  * (trre_compile) is single-threaded host work and trre_last_error() is per thread. */
+/* (overlapping buffers: TRRE_E_ARG, as for trre_scan_host) */
 int trre_scan_host_multi(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len,
                          uint32_t device_mask);
 

@@ -114,3 +114,33 @@ def test_no_barrier_is_left_with_lds_stores_in_flight(tmp_path):
                 "\tds_write_b32 v0, v1\n\ts_cbranch_scc1 .LBB0_1\n\ts_endpgm\n")
     r = subprocess.run([sys.executable, audit, bad], stdout=subprocess.PIPE, check=True)
     assert "BAD ds_write_b32" in r.stdout.decode() and r.stdout.decode().strip().splitlines()[-1] == "barriers flagged: 1"
+
+
+def test_overlapping_buffers_are_refused_without_a_gpu():
+    """include/trre_mi355x.h: on the device path d_in == d_out is a scan in place and any other overlap of [d_in, d_in + n) and
+    [d_out, d_out + cap) is TRRE_E_ARG, answered before the device is touched (made-up pointers, never dereferenced); the host paths
+    refuse every overlap, out == in included"""
+    import numpy as np
+    L = api.lib()
+    p = trre_amd.Program("a:xyz", "dft")
+    m = ctypes.c_size_t()
+    d_in, n = 0x7f0000100000, 1 << 16
+    cases = [(d_in + d, n) for d in (1, 15, 16, 4096, -1, -15, -16, -4096)] + [(d_in + 1 - n, n), (d_in + 1 - 64, 64), (d_in + n - 1, 8)]
+    for d_out, cap in cases:
+        assert L.trre_scan_device(p._h, d_in, n, d_out, cap, ctypes.byref(m), None) == api.E_ARG, (d_out - d_in, cap)
+        assert "overlap" in L.trre_last_error().decode()
+        assert L.trre_scan_enqueue(p._h, d_in, n, d_out, cap, None) == api.E_ARG, (d_out - d_in, cap)
+    # the ranges that only touch are not refused as overlapping (here: no device, so the call gets as far as asking for one)
+    for d_out, cap in [(d_in + n, n), (d_in - n, n), (d_in, n)]:
+        rc = L.trre_scan_device(p._h, d_in, n, d_out, cap, ctypes.byref(m), None)
+        assert rc != api.E_ARG or "overlap" not in L.trre_last_error().decode(), (d_out - d_in, cap)
+    buf = np.zeros(4096, dtype=np.uint8)
+    buf[:2000] = ord("a")
+    buf[1999] = 10
+    src = buf.ctypes.data
+    for out, cap in [(src, 4096), (src, 0), (src + 1, 100), (src + 1999, 2000), (src + 1000, 10)]:
+        for fn in (L.trre_scan_host, L.trre_scan_host_multi):     # (device 0 / device mask 0: never reached)
+            m.value = 12345
+            assert fn(p._h, ctypes.c_char_p(src), 2000, out, cap, ctypes.byref(m), 0) == api.E_ARG, (fn, out - src, cap)
+            assert m.value == 0
+    assert bytes(buf[:1999]) == b"a" * 1999

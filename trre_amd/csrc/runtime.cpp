@@ -99,8 +99,10 @@ struct Pending {
     bool active = false;
     int family = 0;         // what runs
     int asked = 0;          // ... and what the caller's family choice was (a length-preserving family on an input with long lines runs as its general sibling)
-    const uint8_t* d_in = nullptr;
+    const uint8_t* d_in = nullptr;  // what the kernels read: the caller's input, or its snapshot (ScanCtx::d_snap) when the scan is in place
     uint8_t* d_out = nullptr;
+    const uint8_t* user_in = nullptr;  // the caller's input pointer (a batch is the same scan as the caller named it)
+    bool aliased = false;           // d_out is the caller's input: the kernels read the snapshot
     size_t n = 0, cap = 0;
     hipStream_t stream = nullptr;
     bool launched = false;
@@ -110,16 +112,12 @@ struct Pending {
     bool patched = false;                 // the launch was the mark + splice pair of a large table's copy form, not a count / emit pair
     bool one = false;                     // the launch was the one-pass kernel (one_block.hpp), not a count / emit pair
     bool mapgen = false;                  // ... the memoryless one-pass kernel (map_block.hpp)
-    // the stack guard found, before an in-place launch, a line on which the reference's search runs out of stack: nothing was launched
     // exact sub-ranges (scan_block.hpp: ScanArgs::exact): what finish() needs to run repair rounds and the emit pass again
     bool exact = false;
     trre::ScanArgs xargs{};
     int64_t x_lane_bytes = 0, x_n_chunks = 0, x_rev_lane_bytes = 0;
     int x_g16 = 0, x_sym = 0;
     bool x_slow = false, x_ent_lds = false;
-    bool guard_hit = false;
-    uint64_t guard_line = 0;              // where that line starts
-    uint32_t guard_part = 0;              // bytes of its output the reference had printed (in ScanCtx::d_gout), or ~0u: not available
 };
 
 // Everything ONE in-flight scan needs on a device besides the tables: status words, the workspaces of the
@@ -137,6 +135,8 @@ struct ScanCtx {
     uint32_t* d_redo = nullptr;       // window kernel redo list
     int64_t redo_lanes = 0;
     uint8_t* d_sym = nullptr;         // guided families: one symbol per input byte
+    uint8_t* d_snap = nullptr;        // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads
+    size_t snap_bytes = 0;
     uint8_t* d_gen_out = nullptr;     // generator modes: the enumeration's output before it goes down
     size_t gen_out_cap = 0;
     size_t sym_bytes = 0;
@@ -568,6 +568,7 @@ void ctx_free(ScanCtx& c) {
     (void)hipFree(c.d_scratch);
     (void)hipFree(c.d_redo);
     (void)hipFree(c.d_sym);
+    (void)hipFree(c.d_snap);
     (void)hipFree(c.d_gen_out);
     (void)hipFree(c.d_gflags); (void)hipFree(c.d_gruns); (void)hipFree(c.d_gstack); (void)hipFree(c.d_gobuf); (void)hipFree(c.d_gout);
     (void)hipFree(c.d_miss);
@@ -941,38 +942,43 @@ int enqueue(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, const uint8_
     // timing events bracket the whole batch and finish() speaks for the last launch — so every launch of
     // a batch must be the same scan (benchmark loops); anything else has to be finished first.
     const bool batch = pd.active && pd.launched;
-    if (pd.active && (pd.asked != family || pd.d_in != d_in || pd.d_out != d_out || pd.n != n || pd.cap != cap || pd.stream != stream))
+    if (pd.active && (pd.asked != family || pd.user_in != d_in || pd.d_out != d_out || pd.n != n || pd.cap != cap || pd.stream != stream))
         return fail(TRRE_E_ARG, "error: a different scan is still in flight on this device: call trre_scan_finish first");
     const int batch_count = batch ? pd.count : 0;
-    // an in-place scan destroys what the stack guard would look at: it looks first (the first launch of a batch only — the rest
-    // are the same scan).  A line the reference's search fails on: nothing is launched, finish() answers.
-    if (!batch && n && d_in == d_out && guard_applies(*p, *cx, n)) {
-        GuardHit hit;
-        const int grc = guard_check(p, st, cx, d_in, n, stream, &hit);
-        if (grc) return grc;
-        if (hit.hit) {
-            pd = Pending();
-            pd.active = true;
-            pd.family = family; pd.asked = family;
-            pd.d_in = d_in; pd.d_out = d_out; pd.n = n; pd.cap = cap; pd.stream = stream;
-            pd.guard_hit = true; pd.guard_line = hit.line_start; pd.guard_part = hit.part;
-            return TRRE_OK;
+    const uint8_t* const user_in = d_in;
+    // In place (d_in == d_out): the kernels write where they read, and neither a family whose output moves (count / emit, the one-pass
+    // kernels, the lazy and backtracking lanes) nor a relaunch in finish() (a NUL, an overflow, a mask scratch) could read the input
+    // again.  So the scan reads a copy, at the same offset mod 16 (the window kernel's stores stay aligned); the launches of a batch
+    // read the copy the first one made — the caller's buffer holds their output by then.
+    const bool aliased = n && d_in == d_out;
+    if (aliased) {
+        const size_t a0 = reinterpret_cast<uintptr_t>(d_in) & 15u;
+        if (!batch) {
+            if (cx->snap_bytes < n + 16) {
+                if (cx->d_snap) (void)hipFree(cx->d_snap);
+                cx->d_snap = nullptr; cx->snap_bytes = 0;
+                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_snap), n + 16));
+                cx->snap_bytes = n + 16;
+            }
+            HIP_TRY(hipMemcpyAsync(cx->d_snap + a0, d_in, n, hipMemcpyDeviceToDevice, stream));
         }
+        d_in = cx->d_snap + a0;
     }
     pd = Pending();
     pd.active = true;
     pd.count = batch_count;
     pd.family = family; pd.asked = family;
     pd.d_in = d_in; pd.d_out = d_out; pd.n = n; pd.cap = cap; pd.stream = stream;
+    pd.user_in = user_in; pd.aliased = aliased;
     if (n == 0) return TRRE_OK;
     int rc;
     // Long lines (round 5): is there a sample point without a line end within 32 KiB?  Asked once per buffer (a tiny kernel and a wait), for the
     // families that have the exact sub-ranges to answer with; a length-preserving family then runs as its general sibling (count, exclusive sum,
-    // emit: the exact sub-ranges live there), unless the scan is in place.
+    // emit: the exact sub-ranges live there).
     static const int exact_env0 = getenv("TRRE_EXACT") ? atoi(getenv("TRRE_EXACT")) : -1;
     {
         const bool small_tables = (family == TRRE_KERNEL_STREAM_LP && p->stt.g16_ok) || (family == TRRE_KERNEL_GUIDED_LP && p->gt.fwd.g16_ok && !p->gt.wide);
-        if (small_tables && !cx->exact_off && exact_env0 != 0 && d_in != d_out && cap >= n) {
+        if (small_tables && !cx->exact_off && exact_env0 != 0 && cap >= n) {
             if (cx->probe_in != d_in || cx->probe_n != n) {
                 const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
                 ScanArgs pa{};
@@ -1286,11 +1292,11 @@ int enqueue(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, const uint8_
 // position, the rest of the record is gone — so everything behind it moves up.  The kernel listed the NULs; the lines'
 // ends are looked up, and the stretches between the cuts are mapped again from the input to where they belong (the
 // first one is in place already).  Returns TRRE_OK with *out_len, an error, or -1: not a case for this (more NULs than the
-// list holds, more than 256 cut lines, an in-place scan) — the caller runs the buffer through the general family.
+// list holds, more than 256 cut lines) — the caller runs the buffer through the general family.
 int repair_bytemap_nuls(DeviceState* st, ScanCtx* cx, const Pending& was, size_t* out_len) {
     using namespace trre;
     static const bool off = getenv("TRRE_NO_NUL_REPAIR") != nullptr;
-    if (off || was.d_in == was.d_out) return -1;
+    if (off) return -1;
     uint32_t count = 0;
     HIP_TRY(hipMemcpyAsync(&count, cx->d_status + 4, 4, hipMemcpyDeviceToHost, was.stream));
     HIP_TRY(hipStreamSynchronize(was.stream));
@@ -1682,23 +1688,18 @@ int finish_inner(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
 // finish_inner, then the stack guard: a scan that went through may have met a line on which the reference's search runs out of
 // stack (guard_block.hpp) — then the answer is what the reference gives: an error, and the output up to the attempt that
 // overflowed (the lines before that line from a scan of exactly those lines, the line's own part from the guard's search).
-int finish(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
+int finish_guarded(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
     using namespace trre;
     const Pending was = cx->pend;
     // the long-line probe's verdict holds for the batch it was asked in (identical launches); the caller may put other bytes into the same
     // buffer afterwards — the host path's slots do for every chunk — so the next batch asks again
     cx->probe_in = nullptr; cx->probe_n = 0;
     GuardHit hit;
-    if (was.active && was.guard_hit) {                     // found before an in-place launch: nothing has run yet
-        cx->pend = Pending();
-        hit.hit = true; hit.line_start = was.guard_line; hit.part = was.guard_part;
-    } else {
-        const int rc = finish_inner(p, st, cx, out_len);
-        if (rc != TRRE_OK || !was.active || was.n == 0 || !guard_applies(*p, *cx, was.n) || was.d_in == was.d_out) return rc;
-        const int grc = guard_check(p, st, cx, was.d_in, was.n, was.stream, &hit);
-        if (grc) return grc;
-        if (!hit.hit) return rc;
-    }
+    const int rc = finish_inner(p, st, cx, out_len);
+    if (rc != TRRE_OK || !was.active || was.n == 0 || !guard_applies(*p, *cx, was.n)) return rc;
+    const int grc = guard_check(p, st, cx, was.d_in, was.n, was.stream, &hit);     // (in place: the snapshot, which still holds the input)
+    if (grc) return grc;
+    if (!hit.hit) return rc;
     size_t pre = 0;
     if (hit.line_start > 0) {
         cx->guard_off = true;
@@ -1717,6 +1718,18 @@ int finish(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
     }
     cx->relaunches += 1;
     return fail(TRRE_E_DIVERGES, kStackMsg);
+}
+
+// finish_guarded, and the promise of an in-place scan that asks for room: the caller's buffer holds its input again (the emit pass
+// may have written the chunks that fit), so the size query and the retry from the same buffer work as with separate buffers
+int finish(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
+    const Pending was = cx->pend;
+    const int rc = finish_guarded(p, st, cx, out_len);
+    if (rc == TRRE_E_CAPACITY && was.active && was.aliased) {
+        HIP_TRY(hipMemcpyAsync(was.d_out, was.d_in, was.n, hipMemcpyDeviceToDevice, was.stream));
+        HIP_TRY(hipStreamSynchronize(was.stream));
+    }
+    return rc;
 }
 
 
@@ -2011,6 +2024,19 @@ int trre_debug_lazy_explore(trre_prog* p, const uint32_t* misses, size_t n, size
     return TRRE_OK;
 }
 
+// [a, a + n) and [b, b + m) share a byte (no pointer is dereferenced, no sum can wrap)
+static bool ranges_overlap(const void* a, size_t n, const void* b, size_t m) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return n && m && (x >= y ? x - y < m : y - x < n);
+}
+
+// the device path: d_in == d_out is a scan in place; any other overlap is refused before anything touches the device
+static int device_overlap(const uint8_t* d_in, size_t n, const uint8_t* d_out, size_t cap) {
+    if (d_in != d_out && ranges_overlap(d_in, n, d_out, cap))
+        return fail(TRRE_E_ARG, "error: input and output overlap (only d_in == d_out, a scan in place, is allowed)");
+    return TRRE_OK;
+}
+
 // the prog's state on the calling thread's current device
 static int current_state(trre_prog* p, DeviceState** st) {
     int dev = 0;
@@ -2021,6 +2047,7 @@ static int current_state(trre_prog* p, DeviceState** st) {
 int trre_scan_enqueue(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, void* stream) {
     g_scan_flags = 0;
     if (!p || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
+    if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     DeviceState* st;
     int rc = current_state(p, &st);
     if (rc) return rc;
@@ -2173,6 +2200,7 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
                      void* stream) {
     g_scan_flags = 0;
     if (!p || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
+    if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     DeviceState* st;
     int rc = current_state(p, &st);
     if (rc) return rc;
@@ -2478,10 +2506,18 @@ struct DeviceScope {
 };
 }  // namespace
 
+// the host paths stage their chunks anyway: a scan in place saves nothing there, and any overlap (out == in too) is refused
+static int host_overlap(const uint8_t* in, size_t n, const uint8_t* out, size_t cap) {
+    if (n && out && (out == in || ranges_overlap(in, n, out, cap)))
+        return fail(TRRE_E_ARG, "error: input and output overlap (the host paths take separate buffers)");
+    return TRRE_OK;
+}
+
 int trre_scan_host(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len, int device) {
     g_scan_flags = 0;
     if (!p || (n && !in) || (cap && !out)) return fail(TRRE_E_ARG, "error: null argument");
     if (out_len) *out_len = 0;
+    if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     if (n == 0) return TRRE_OK;
     DeviceScope scope(device);
     HIP_TRY(scope.err);
@@ -2584,6 +2620,7 @@ int trre_scan_host_multi(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out
     g_scan_flags = 0;
     if (!p || (n && !in) || (cap && !out)) return fail(TRRE_E_ARG, "error: null argument");
     if (out_len) *out_len = 0;
+    if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     int n_dev = 0;
     {
         static const bool trace_on = getenv("TRRE_TRACE") != nullptr;
