@@ -160,6 +160,29 @@ size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_
 int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, size_t* out_len,
                      void* stream);
 
+/* Ragged records: a batch of separate strings held as one packed byte buffer plus int64 offsets (Arrow string columns,
+ * torch.nested, HF datasets).  Record i is d_in[d_off[i] .. d_off[i+1]) for i < nrec; d_off (nrec + 1 entries, device memory)
+ * starts at 0, ends at n and never decreases.  Record i's output is exactly what trre_scan_device gives for that record alone,
+ * i.e. what the reference prints for it as its input file (printf '%s' "$rec" | trre P); the outputs are concatenated into
+ * d_out, and d_out_off[i] (nrec + 1 entries, device memory) is where record i's output starts, d_out_off[nrec] = *out_len.
+ * The reference's framing holds per record: a record may hold several lines; a record whose last byte is not '\n' loses that
+ * byte and still prints a '\n' (printf 'abc' | trre 'c:X' prints "ab\n", as for "ab\n"); an empty record prints nothing; a NUL
+ * cuts its line.  nrec == 0 is valid with n == 0 (d_out_off[0] = 0); n == 0 makes every record empty.
+ * How: a copy of the input whose records' last bytes are '\n' is scanned as it stands (same family, same kernels), and every
+ * line prints exactly one framing '\n', so record i's output ends just past the output newline that ends its last line.
+ * Refused with TRRE_E_UNSUPPORTED before the device is touched: match and generator modes (a line prints zero or many
+ * newlines there) and a program that can print a '\n' of its own (a raw newline on the output side, an output range over
+ * 0x0a; byte copies such as '.', '[a-z]', '[a:A-z:Z]' are taken).  Bad offsets (checked on the device, one status word
+ * read back): TRRE_E_ARG, nothing written to d_out or d_out_off.  Any overlap of d_off or d_out_off with the data buffers or
+ * with each other: TRRE_E_ARG; d_in / d_out as for trre_scan_device (d_in == d_out, in place, is valid).  TRRE_E_CAPACITY:
+ * *out_len is the size needed, d_out_off is unspecified, in place the first n bytes hold the input again: a retry with the
+ * same arguments works.  TRRE_E_DIVERGES: d_out and *out_len are what the scan of all records gives — the outputs of the
+ * records before the failing one and the failing record's partial output; d_out_off is unspecified.  A split-form scan
+ * still in flight on this (prog, device): TRRE_E_ARG.  Synchronous with respect to `stream`; trre_last_scan_flags as for
+ * trre_scan_device.  Device memory: n + 32 bytes of staging and 24 bytes per 64 KiB of input and of output. */
+int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
+                             size_t cap, int64_t* d_out_off, size_t* out_len, void* stream);
+
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */
 #define TRRE_SCAN_GUARD_UNDECIDED 1u /* NFT engine: the input holds a line long enough to exhaust the reference's 65 536-item stack

@@ -90,6 +90,8 @@ struct Nft {
 // with_initial_join: the deterministic engine's automaton starts with an extra
 // JOIN so that the start state is never a CONS (trre_dft.c:516-523).
 Nft build_nft(const Ast& ast, bool with_initial_join);
+// the program can print a '\n' of its own (a PROD of '\n' not entered by consuming one): outside what the records path takes
+bool nft_prints_newline(const Nft& nft);
 
 // ---- deterministic transducer (eager subset construction) ---------------------
 constexpr int32_t kEdgeDead = -1, kEdgeDiverge = -2;

@@ -11,6 +11,7 @@ struct GuardArgs;
 struct LazyArgs;
 struct OneArgs;
 struct MapGenArgs;
+struct RecArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -74,6 +75,17 @@ void launch_line_probe(const ScanArgs& a, int64_t window, uint32_t* out, void* s
 void launch_chunk_scan(const uint64_t* total, uint64_t* base, int64_t n_chunks, void* stream);
 void launch_bytemap(const ScanArgs& a, void* stream);
 void launch_nul_eol(const uint8_t* in, int64_t n, const uint64_t* pos, uint64_t* eol, uint32_t count, void* stream);
+// ragged records (records_block.hpp): bytes per tile; the offsets' check (status |= 1 when bad); the first record of every
+// tile (side 0: by end offset over the input's tiles, 1: by rank over the output's); staging; ranks; the output's '\n' per
+// tile; the output offsets (status |= 1 when a rank falls outside its tile); the replaced bytes back into dst
+int64_t rec_tile_bytes();
+void launch_rec_check(const int64_t* off, int64_t nrec, int64_t n, uint32_t* status, void* stream);
+void launch_rec_part(int side, const RecArgs& a, int64_t tiles, void* stream);
+void launch_rec_stage(const RecArgs& a, int64_t tiles, void* stream);
+void launch_rec_rank(const RecArgs& a, void* stream);
+void launch_rec_count(const RecArgs& a, int64_t tiles, void* stream);
+void launch_rec_locate(const RecArgs& a, int64_t tiles, uint32_t* status, void* stream);
+void launch_rec_restore(const RecArgs& a, uint8_t* dst, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

@@ -186,4 +186,21 @@ Nft build_nft(const Ast& ast, bool with_initial_join) {
     return nft;
 }
 
+// A produced '\n' prints unless the state can only be entered by consuming a '\n' (copy mode and 'x:y' pairs put a PROD right
+// behind its CONS), which a line never holds: so '.', '[a-z]', '[a:A-z:Z]' print none, ':\n' and '[a:\t-c:\x0b]' do.
+bool nft_prints_newline(const Nft& nft) {
+    const int32_t n = (int32_t)nft.st.size();
+    std::vector<uint8_t> guarded(n, 1);          // every way in is a CONS of '\n' (so far)
+    guarded[nft.start] = 0;
+    for (int32_t s = 0; s < n; ++s) {
+        const NState& q = nft.st[s];
+        const bool nl_cons = q.kind == NKind::Cons && q.val == (uint8_t)'\n';
+        for (int32_t t : {q.a, q.b})
+            if (t >= 0 && !nl_cons) guarded[t] = 0;
+    }
+    for (int32_t s = 0; s < n; ++s)
+        if (nft.st[s].kind == NKind::Prod && nft.st[s].val == (uint8_t)'\n' && !guarded[s]) return true;
+    return false;
+}
+
 }  // namespace trre

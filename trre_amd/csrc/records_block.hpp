@@ -1,0 +1,285 @@
+// records_block.hpp — per-thread bodies of the ragged-records passes (trre_scan_device_records).
+//
+// Records are in[off[i] .. off[i+1]).  Record i alone prints what the reference prints for it as a file: its lines, the last
+// one cut one byte short (getline's record minus its last byte, trre_nft.c:775-790).  So a copy of the input in which the last
+// byte of every non-empty record is '\n' (the STAGED copy) holds exactly the records' lines, and the plain scan of that copy is
+// the concatenation of the records' outputs.  In scan mode every line prints exactly one framing '\n' and, for the programs this
+// path takes (runtime.cpp: prints_newline), no other: record i's output ends just past output newline number R_i, where
+//     R_i = number of '\n' in staged[0, off[i+1])
+// (an empty record has the R of the record before it, and prints nothing).  The passes:
+//   k_rec_check   the offsets: off[0] = 0, off[nrec] = n, no decrease (a status word)
+//   k_rec_part    the first record of every tile (a binary search per tile: the merge-path partition of records against tiles)
+//   k_rec_stage   input tile -> staged copy, '\n' per tile, the tile-local R of every record whose end lies in the tile
+//   k_chunk_scan  the tiles' bases
+//   k_rec_rank    R_i = tile base + local rank, parked in out_off[i + 1] (bits 0..55; bits 56..63: the replaced byte, in place)
+//   (the plain scan of the staged copy)
+//   k_rec_count   '\n' per output tile;  k_chunk_scan;  k_rec_part on the ranks
+//   k_rec_locate  out_off[i + 1] = position of output newline R_i, + 1
+//   k_rec_restore (in place, TRRE_E_CAPACITY) the replaced bytes back into the caller's buffer
+// Tiles are TILE bytes of the 16-byte aligned v-space (v = position + vbeg, vbeg = the buffer's address mod 16).  A tile's
+// bytes are held as one 16-bit '\n' mask per 16-byte vector in LDS; a thread owns VECS consecutive vectors for the ranks, and
+// a workgroup-wide exclusive scan of the threads' counts gives every position its rank in the tile.
+//
+// Written once as TRRE_HD functions: scan_kernels.hip instantiates them for the device, tests/records_shim.cpp runs them on the
+// host thread by thread (barriers are loop boundaries) against numpy.
+#pragma once
+#include <cstdint>
+
+#include "scan_block.hpp"
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TRRE_REC_LDS_OR(p, v) atomicOr((p), (v))
+#else
+#define TRRE_REC_LDS_OR(p, v) (*(p) |= (v))
+#endif
+
+namespace trre {
+
+constexpr int kRecThreads = 256;
+constexpr int kRecVecs = 16;                          // 16-byte vectors per thread: 64 KiB tiles
+constexpr uint64_t kRecRankMask = (1ull << 56) - 1;   // a rank; bits 56..63 hold the byte the staged copy replaced
+
+template <int THREADS_, int VECS_>
+struct RecGeo {
+    static constexpr int THREADS = THREADS_;
+    static constexpr int VECS = VECS_;
+    static constexpr int64_t TILE = (int64_t)THREADS_ * VECS_ * 16;
+    static constexpr int NVEC = THREADS_ * VECS_;     // 16-bit masks in LDS
+};
+using RecGeoDev = RecGeo<kRecThreads, kRecVecs>;
+
+struct RecArgs {
+    const uint8_t* in_v0;   // the buffer the tiles are over (input; output for k_rec_count / k_rec_locate) - vbeg, 16-byte aligned
+    uint8_t* snap_v0;       // the staged copy, same geometry as the input
+    int64_t vbeg, vend;     // valid bytes: v in [vbeg, vend)
+    const int64_t* off;     // [nrec + 1] the caller's record offsets
+    int64_t nrec;
+    int64_t* out_off;       // [nrec + 1] ranks, then output offsets
+    int64_t* part;          // [tiles + 1] first record of each tile
+    uint64_t* cnt;          // [tiles] '\n' per tile
+    const uint64_t* base;   // [tiles + 1] exclusive scan of cnt
+    uint32_t keep;          // in place: park the replaced byte in bits 56..63 of the rank (k_rec_restore)
+};
+
+TRRE_HD uint32_t rec_popc(uint32_t x) { return (uint32_t)__builtin_popcount(x); }
+
+// bad offsets: off[0] != 0, off[nrec] != n, off[i] > off[i + 1]; k in [0, nrec]
+TRRE_HD uint32_t rec_check(const int64_t* off, int64_t nrec, int64_t n, int64_t k) {
+    uint32_t bad = 0;
+    if (k == 0 && off[0] != 0) bad = 1;
+    if (k == nrec && off[nrec] != n) bad = 1;
+    if (k < nrec && off[k] > off[k + 1]) bad = 1;
+    return bad;
+}
+
+// first k in [0, n) with key(k) >= x, n when there is none (keys do not decrease)
+template <class Key>
+TRRE_HD int64_t rec_lower_bound(const Key& key, int64_t n, int64_t x) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (key(mid) < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+struct RecEndKey {   // record i's end offset
+    const int64_t* off;
+    TRRE_HD int64_t operator()(int64_t i) const { return off[i + 1]; }
+};
+struct RecRankKey {  // record i's rank
+    const int64_t* out_off;
+    TRRE_HD int64_t operator()(int64_t i) const { return (int64_t)((uint64_t)out_off[i + 1] & kRecRankMask); }
+};
+
+// the tile that holds the end of a record ending at offset p (its last byte; p == 0: tile 0)
+TRRE_HD int64_t rec_end_tile(int64_t p, int64_t vbeg, int64_t tile) { return p == 0 ? 0 : (p - 1 + vbeg) / tile; }
+
+// k_rec_part, input side: part[b] = the first record whose end lies in tile b or after it (b in [0, tiles])
+TRRE_HD void rec_part_in(const RecArgs& a, int64_t tile, int64_t b) {
+    a.part[b] = b == 0 ? 0 : rec_lower_bound(RecEndKey{a.off}, a.nrec, b * tile - a.vbeg + 1);
+}
+// ... output side: the first record whose newline lies in tile b or after it (rank > base[b])
+TRRE_HD void rec_part_out(const RecArgs& a, int64_t b) {
+    a.part[b] = b == 0 ? 0 : rec_lower_bound(RecRankKey{a.out_off}, a.nrec, (int64_t)a.base[b] + 1);
+}
+
+// 16 bytes from v-space position v (16-byte aligned): non-temporal on the device (each byte is read once)
+TRRE_HD U128 rec_load16(const uint8_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const U128* s = reinterpret_cast<const U128*>(p);
+    U128 w;
+    w.x = __builtin_nontemporal_load(&s->x); w.y = __builtin_nontemporal_load(&s->y);
+    w.z = __builtin_nontemporal_load(&s->z); w.w = __builtin_nontemporal_load(&s->w);
+    return w;
+#else
+    return *reinterpret_cast<const U128*>(p);
+#endif
+}
+
+TRRE_HD void rec_store16(uint8_t* p, const U128& w) {
+    U128* d = reinterpret_cast<U128*>(p);
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_nontemporal_store(w.x, &d->x); __builtin_nontemporal_store(w.y, &d->y);
+    __builtin_nontemporal_store(w.z, &d->z); __builtin_nontemporal_store(w.w, &d->w);
+#else
+    *d = w;
+#endif
+}
+
+// 4-bit mask of the bytes of w that are '\n' (SWAR zero-byte test of w ^ 0x0a0a0a0a, exact: no carry crosses a byte)
+TRRE_HD uint32_t rec_nl4(uint32_t w) {
+    const uint32_t x = w ^ 0x0a0a0a0au;
+    const uint32_t z = ~((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x)) & 0x80808080u;
+    return (((z >> 7) * 0x00204081u) >> 21) & 0xfu;
+}
+TRRE_HD uint32_t rec_nl16(const U128& w) { return rec_nl4(w.x) | rec_nl4(w.y) << 4 | rec_nl4(w.z) << 8 | rec_nl4(w.w) << 12; }
+// the bytes of the vector at v that lie in [vbeg, vend), as a 16-bit mask
+TRRE_HD uint32_t rec_valid16(int64_t v, int64_t vbeg, int64_t vend) {
+    uint32_t m = 0xffffu;
+    if (v < vbeg) m &= 0xffffu << (uint32_t)(vbeg - v);
+    if (vend - v < 16) m &= (1u << (uint32_t)(vend - v)) - 1u;
+    return m;
+}
+// the bytes of w named by the 4-bit mask m become '\n'
+TRRE_HD uint32_t rec_put_nl4(uint32_t w, uint32_t m) {
+    const uint32_t e = ((m * 0x00204081u) & 0x01010101u) * 0xffu;
+    return (w & ~e) | (0x0a0a0a0au & e);
+}
+
+// k_rec_stage, before the marks: the thread's vectors of tile b (vector q = j * THREADS + tid: coalesced), asked for at once
+template <class G>
+TRRE_HD void rec_load_vecs(const RecArgs& a, int64_t b, int tid, U128 (&w)[G::VECS]) {
+    for (int j = 0; j < G::VECS; ++j) {
+        const int64_t v = b * G::TILE + 16 * ((int64_t)j * G::THREADS + tid);
+        if (v < a.vend) w[j] = rec_load16(a.in_v0 + v);
+    }
+}
+// ... the marks: a bit per record end in the tile (bits32: TILE / 32 words, zeroed before)
+template <class G>
+TRRE_HD void rec_mark(const RecArgs& a, int64_t b, int tid, uint32_t* bits32) {
+    const int64_t i1 = a.part[b + 1];
+    for (int64_t i = a.part[b] + tid; i < i1; i += G::THREADS) {
+        const int64_t p = a.off[i + 1];
+        if (p > a.off[i]) {
+            const int64_t x = p - 1 + a.vbeg - b * G::TILE;
+            TRRE_REC_LDS_OR(bits32 + (x >> 5), 1u << (uint32_t)(x & 31));
+        }
+    }
+}
+// ... the staged vectors out, and in place of each vector's marks its '\n' mask (valid bytes only); returns the thread's count
+template <class G>
+TRRE_HD uint32_t rec_stage_vecs(const RecArgs& a, int64_t b, int tid, U128 (&w)[G::VECS], uint16_t* bits16) {
+    uint32_t c = 0;
+    for (int j = 0; j < G::VECS; ++j) {
+        const int q = j * G::THREADS + tid;
+        const int64_t v = b * G::TILE + 16 * (int64_t)q;
+        if (v >= a.vend) { bits16[q] = 0; continue; }
+        const uint32_t mk = bits16[q];
+        U128 r = w[j];
+        if (mk) {
+            r.x = rec_put_nl4(r.x, mk & 15u); r.y = rec_put_nl4(r.y, (mk >> 4) & 15u);
+            r.z = rec_put_nl4(r.z, (mk >> 8) & 15u); r.w = rec_put_nl4(r.w, mk >> 12);
+        }
+        rec_store16(a.snap_v0 + v, r);
+        const uint32_t nl = rec_nl16(r) & rec_valid16(v, a.vbeg, a.vend);
+        bits16[q] = (uint16_t)nl;
+        c += rec_popc(nl);
+    }
+    return c;
+}
+// k_rec_count / k_rec_locate: the '\n' masks of the thread's vectors of an output tile (bits16 may be null: count only)
+template <class G>
+TRRE_HD uint32_t rec_count_vecs(const RecArgs& a, int64_t b, int tid, uint16_t* bits16) {
+    U128 w[G::VECS];
+    for (int j = 0; j < G::VECS; ++j) {
+        const int64_t v = b * G::TILE + 16 * ((int64_t)j * G::THREADS + tid);
+        if (v < a.vend) w[j] = rec_load16(a.in_v0 + v);
+    }
+    uint32_t c = 0;
+    for (int j = 0; j < G::VECS; ++j) {
+        const int q = j * G::THREADS + tid;
+        const int64_t v = b * G::TILE + 16 * (int64_t)q;
+        const uint32_t nl = v < a.vend ? rec_nl16(w[j]) & rec_valid16(v, a.vbeg, a.vend) : 0u;
+        if (bits16) bits16[q] = (uint16_t)nl;
+        c += rec_popc(nl);
+    }
+    return c;
+}
+// '\n' in the thread's rank segment: vectors [tid * VECS, tid * VECS + VECS)
+template <class G>
+TRRE_HD uint32_t rec_seg_count(const uint16_t* bits16, int tid) {
+    uint32_t c = 0;
+    for (int k = 0; k < G::VECS; ++k) c += rec_popc(bits16[tid * G::VECS + k]);
+    return c;
+}
+// '\n' of the tile at byte indices <= x (pre: the segments' exclusive prefix)
+template <class G>
+TRRE_HD uint32_t rec_rank_at(const uint16_t* bits16, const uint32_t* pre, int64_t x) {
+    const int q = (int)(x >> 4), t = q / G::VECS;
+    uint32_t r = pre[t];
+    for (int k = t * G::VECS; k < q; ++k) r += rec_popc(bits16[k]);
+    return r + rec_popc(bits16[q] & ((2u << (uint32_t)(x & 15)) - 1u));
+}
+// k_rec_stage, last: the tile-local rank of every record whose end lies in tile b, into out_off[i + 1]
+template <class G>
+TRRE_HD void rec_rank_records(const RecArgs& a, int64_t b, int tid, const uint16_t* bits16, const uint32_t* pre) {
+    const int64_t i1 = a.part[b + 1];
+    for (int64_t i = a.part[b] + tid; i < i1; i += G::THREADS) {
+        const int64_t p = a.off[i + 1];
+        uint64_t r = 0;
+        if (p > 0) {
+            const int64_t x = p - 1 + a.vbeg - b * G::TILE;
+            r = rec_rank_at<G>(bits16, pre, x);
+            if (a.keep && p > a.off[i]) r |= (uint64_t)a.in_v0[b * G::TILE + x] << 56;
+        }
+        a.out_off[i + 1] = (int64_t)r;
+    }
+}
+// k_rec_rank: the tile's base onto record i's local rank
+TRRE_HD void rec_add_base(const RecArgs& a, int64_t tile, int64_t i) {
+    a.out_off[i + 1] = (int64_t)((uint64_t)a.out_off[i + 1] + a.base[rec_end_tile(a.off[i + 1], a.vbeg, tile)]);
+}
+// byte index in the tile of its r-th '\n' (1-based; r <= the tile's count)
+template <class G>
+TRRE_HD int64_t rec_select(const uint16_t* bits16, const uint32_t* pre, uint32_t r) {
+    int lo = 0, hi = G::THREADS - 1;                     // the last segment whose prefix is below r
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (pre[mid] < r) lo = mid;
+        else hi = mid - 1;
+    }
+    r -= pre[lo];
+    int q = lo * G::VECS;
+    for (int k = 0; k < G::VECS; ++k, ++q) {
+        const uint32_t c = rec_popc(bits16[q]);
+        if (r <= c) break;
+        r -= c;
+    }
+    uint32_t m = bits16[q];
+    for (; r > 1; --r) m &= m - 1u;
+    return 16 * (int64_t)q + __builtin_ctz(m);
+}
+// k_rec_locate: out_off[i + 1] for the records whose newline lies in output tile b (total: the tile's '\n'); returns 1 when a
+// rank falls outside the tile (the staging identity broken: an internal error)
+template <class G>
+TRRE_HD uint32_t rec_locate_records(const RecArgs& a, int64_t b, int tid, const uint16_t* bits16, const uint32_t* pre, uint32_t total) {
+    uint32_t bad = 0;
+    if (b == 0 && tid == 0) a.out_off[0] = 0;
+    const int64_t i1 = a.part[b + 1];
+    for (int64_t i = a.part[b] + tid; i < i1; i += G::THREADS) {
+        const uint64_t rk = (uint64_t)a.out_off[i + 1] & kRecRankMask;
+        if (rk <= a.base[0]) { a.out_off[i + 1] = 0; continue; }       // no newline up to the record's end (base[0] is 0)
+        const uint64_t r = rk - a.base[b];
+        if (rk <= a.base[b] || r > total) { bad = 1; continue; }
+        a.out_off[i + 1] = b * G::TILE + rec_select<G>(bits16, pre, (uint32_t)r) - a.vbeg + 1;
+    }
+    return bad;
+}
+// k_rec_restore: record i's replaced byte back (dst: the caller's buffer, which holds the staged copy again)
+TRRE_HD void rec_restore(const RecArgs& a, uint8_t* dst, int64_t i) {
+    const int64_t p = a.off[i + 1];
+    if (p > a.off[i]) dst[p - 1] = (uint8_t)((uint64_t)a.out_off[i + 1] >> 56);
+}
+
+}  // namespace trre

@@ -32,6 +32,7 @@
 #include "one_block.hpp"
 #include "map_block.hpp"
 #include "guard_block.hpp"
+#include "records_block.hpp"
 
 namespace {
 
@@ -135,8 +136,10 @@ struct ScanCtx {
     uint32_t* d_redo = nullptr;       // window kernel redo list
     int64_t redo_lanes = 0;
     uint8_t* d_sym = nullptr;         // guided families: one symbol per input byte
-    uint8_t* d_snap = nullptr;        // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads
-    size_t snap_bytes = 0;
+    uint8_t* d_snap = nullptr;        // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads;
+    size_t snap_bytes = 0;            // trre_scan_device_records: the staged copy, which the scan reads
+    uint64_t* d_rec = nullptr;        // trre_scan_device_records: status word, then part [tiles + 1], cnt [tiles], base [tiles + 1]
+    int64_t rec_tiles = 0;
     uint8_t* d_gen_out = nullptr;     // generator modes: the enumeration's output before it goes down
     size_t gen_out_cap = 0;
     size_t sym_bytes = 0;
@@ -228,6 +231,7 @@ struct trre_prog {
     trre::GuidedTables gt;
     trre::GenTables gen;              // generator modes (`-a`): viability DFA for the device, follow lists for the host enumeration
     int mode = TRRE_MODE_SCAN;
+    bool prints_newline = false;      // a '\n' of the program's own can be printed (nft_prints_newline): no records path
     uint32_t nft_nodes = 0;
     bool has_engine_tables = false;   // tile kernels available (always for DFT; NFT: <= 64 nodes, no epsilon cycle)
     std::vector<uint8_t> blob;
@@ -569,6 +573,7 @@ void ctx_free(ScanCtx& c) {
     (void)hipFree(c.d_redo);
     (void)hipFree(c.d_sym);
     (void)hipFree(c.d_snap);
+    (void)hipFree(c.d_rec);
     (void)hipFree(c.d_gen_out);
     (void)hipFree(c.d_gflags); (void)hipFree(c.d_gruns); (void)hipFree(c.d_gstack); (void)hipFree(c.d_gobuf); (void)hipFree(c.d_gout);
     (void)hipFree(c.d_miss);
@@ -1750,6 +1755,7 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
         Nft nft = build_nft(ast, engine == TRRE_ENGINE_DFT);
         p->nft_states = (uint32_t)nft.st.size();
         p->nft_cons = (uint32_t)nft.n_cons;
+        p->prints_newline = nft_prints_newline(nft);
         // the stack guard (guard_block.hpp): the NFT itself, for the lines long enough to exhaust the reference's stack
         auto make_guard = [&](bool match) {
             p->guard = build_guard(nft);
@@ -2231,6 +2237,125 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
     rc = enqueue(p, st, &st->ctx, fam, d_in, n, d_out, cap, static_cast<hipStream_t>(stream));
     if (rc) { st->ctx.pend = Pending(); return rc; }
     return finish(p, st, &st->ctx, out_len);
+}
+
+// ---- ragged records (records_block.hpp) ----------------------------------------------------------------------------------
+// status word, part [tiles + 1], cnt [tiles], base [tiles + 1]
+static int rec_room(ScanCtx* cx, int64_t tiles) {
+    if (tiles <= cx->rec_tiles) return TRRE_OK;
+    (void)hipFree(cx->d_rec);
+    cx->d_rec = nullptr; cx->rec_tiles = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_rec), (size_t)(3 * tiles + 3) * 8));
+    cx->rec_tiles = tiles;
+    return TRRE_OK;
+}
+static void rec_carve(ScanCtx* cx, int64_t tiles, trre::RecArgs& a) {
+    a.part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    a.cnt = cx->d_rec + 2 + tiles;
+    a.base = cx->d_rec + 2 + 2 * tiles;
+}
+static int rec_status(ScanCtx* cx, hipStream_t s, uint64_t* extra_dev, uint64_t* extra) {
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, cx->d_rec, 4, hipMemcpyDeviceToHost, s));
+    if (extra_dev) HIP_TRY(hipMemcpyAsync(extra, extra_dev, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return bad ? 1 : 0;
+}
+
+static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
+                      size_t cap, int64_t* d_out_off, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    const int64_t T = rec_tile_bytes();
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    const int64_t tiles = n ? (a0 + (int64_t)n + T - 1) / T : 0;
+    int rc = rec_room(cx, std::max<int64_t>(tiles, 1));
+    if (rc) return rc;
+    // 1. the offsets, on the device: nothing is written before they pass
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec), s);
+    const int bad = rec_status(cx, s, nullptr, nullptr);
+    if (bad < 0) return TRRE_E_DEVICE;
+    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    if (n == 0) {                                        // every record is empty
+        HIP_TRY(hipMemsetAsync(d_out_off, 0, (nrec + 1) * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 2. the staged copy (the snapshot buffer, at the input's offset mod 16, whole 16-byte vectors) and the ranks
+    if (cx->snap_bytes < n + 32) {
+        if (cx->d_snap) (void)hipFree(cx->d_snap);
+        cx->d_snap = nullptr; cx->snap_bytes = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_snap), n + 32));
+        cx->snap_bytes = n + 32;
+    }
+    RecArgs ra{};
+    ra.in_v0 = d_in - a0; ra.snap_v0 = cx->d_snap; ra.vbeg = a0; ra.vend = a0 + (int64_t)n;
+    ra.off = d_off; ra.nrec = (int64_t)nrec; ra.out_off = d_out_off; ra.keep = d_in == d_out ? 1u : 0u;
+    rec_carve(cx, tiles, ra);
+    launch_rec_part(0, ra, tiles, s);
+    launch_rec_stage(ra, tiles, s);
+    launch_chunk_scan(ra.cnt, const_cast<uint64_t*>(ra.base), tiles, s);
+    launch_rec_rank(ra, s);
+    // 3. the plain scan of the staged copy, family as chosen for the program
+    rc = enqueue(p, st, cx, scan_family(*p), cx->d_snap + a0, n, d_out, cap, s);
+    if (rc) { cx->pend = Pending(); return rc; }
+    size_t m = 0;
+    rc = finish(p, st, cx, &m);
+    if (out_len) *out_len = m;
+    if (rc == TRRE_E_CAPACITY && ra.keep) {               // in place: the caller's buffer holds the input again for the retry
+        HIP_TRY(hipMemcpyAsync(d_out, cx->d_snap + a0, n, hipMemcpyDeviceToDevice, s));
+        launch_rec_restore(ra, d_out, s);
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (rc) return rc;
+    if (m == 0) {
+        HIP_TRY(hipMemsetAsync(d_out_off, 0, (nrec + 1) * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 4. record i's output ends just past output newline number R_i
+    const int64_t b0 = (int64_t)(reinterpret_cast<uintptr_t>(d_out) & 15u);
+    const int64_t otiles = (b0 + (int64_t)m + T - 1) / T;
+    rc = rec_room(cx, otiles);
+    if (rc) return rc;
+    RecArgs oa = ra;
+    oa.in_v0 = d_out - b0; oa.vbeg = b0; oa.vend = b0 + (int64_t)m;
+    rec_carve(cx, otiles, oa);
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec);
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_count(oa, otiles, s);
+    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
+    launch_rec_part(1, oa, otiles, s);
+    launch_rec_locate(oa, otiles, d_bad, s);
+    uint64_t last = 0;
+    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(d_out_off + nrec), &last);
+    if (lost < 0) return TRRE_E_DEVICE;
+    if (lost || last != m) return fail(TRRE_E_DEVICE, "error: the records' output offsets do not add up (internal)");
+    return TRRE_OK;
+}
+
+int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                             int64_t* d_out_off, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (!p || !d_off || !d_out_off || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_SCAN)
+        return fail(TRRE_E_UNSUPPORTED, "error: records are offered in scan mode only (a line of -m, -a, -ma prints zero or many newlines)");
+    if (p->prints_newline)
+        return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: record outputs could not be told apart");
+    if (nrec >= ((size_t)1 << 58) || n >= ((size_t)1 << 56)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
+    const size_t ob = (nrec + 1) * 8;
+    if (ranges_overlap(d_off, ob, d_out_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
+        ranges_overlap(d_out_off, ob, d_in, n) || ranges_overlap(d_out_off, ob, d_out, cap))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or the other offsets array");
+    DeviceState* st;
+    int rc = current_state(p, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return records_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
 }
 
 namespace {

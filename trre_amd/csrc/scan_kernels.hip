@@ -12,6 +12,8 @@
 //   k_chunk_scan  exclusive scan of the chunk totals (one workgroup).
 //   k_scan_emit   general tables, pass 2: lane offsets by workgroup scan, lines
 //                 emitted into an LDS staging tile, coalesced copy-out.
+//   k_rec_*       ragged records (trre_scan_device_records): staging, ranks and
+//                 per-record output offsets around the plain scan (records_block.hpp).
 //
 // The per-thread phase bodies live in scan_block.hpp / scan_core.hpp.
 #include <hip/hip_runtime.h>
@@ -26,6 +28,7 @@
 #include "gen_block.hpp"
 #include "lazy_block.hpp"
 #include "guard_block.hpp"
+#include "records_block.hpp"
 
 namespace trre {
 namespace {
@@ -1725,6 +1728,124 @@ void launch_bytemap(const ScanArgs& a, void* stream) {
     int64_t blocks = (nvec + per_block - 1) / per_block;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL((k_bytemap<kUnroll, true>), dim3((unsigned)blocks), dim3(kMapThreads), 0, static_cast<hipStream_t>(stream), a, nvec);
+}
+
+// ---- ragged records (records_block.hpp; runtime.cpp: trre_scan_device_records) --------------------------------------------
+using RG = RecGeoDev;
+
+// exclusive scan of one count per thread over the workgroup (pre[tid]); returns the workgroup's total
+__device__ __forceinline__ uint32_t rec_block_scan(uint32_t s, uint32_t* pre, uint32_t* wtot) {
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    const uint32_t inc = wave_scan_incl(s);
+    if (lane == kWave - 1) wtot[w] = inc;
+    __syncthreads();
+    uint32_t below = 0, total = 0;
+    for (int k = 0; k < RG::THREADS / kWave; ++k) {
+        const uint32_t t = wtot[k];
+        below += k < w ? t : 0u;
+        total += t;
+    }
+    pre[tid] = below + inc - s;
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(256) void k_rec_check(const int64_t* off, int64_t nrec, int64_t n, uint32_t* status) {
+    uint32_t bad = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k <= nrec; k += stride) bad |= rec_check(off, nrec, n, k);
+    bad = wave_or(bad);
+    if ((threadIdx.x & (kWave - 1)) == 0 && bad) atomicOr(status, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_rec_part(RecArgs a, int64_t tiles, int side) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b > tiles) return;
+    if (side == 0) rec_part_in(a, RG::TILE, b);
+    else rec_part_out(a, b);
+}
+
+__global__ __launch_bounds__(RG::THREADS) void k_rec_stage(RecArgs a) {
+    __shared__ uint32_t bits32[RG::NVEC / 2];
+    __shared__ uint32_t pre[RG::THREADS];
+    __shared__ uint32_t wtot[RG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    U128 w[RG::VECS];
+    rec_load_vecs<RG>(a, b, tid, w);                 // the tile's bytes are on their way while the record ends are looked up
+    for (int k = tid; k < RG::NVEC / 2; k += RG::THREADS) bits32[k] = 0;
+    __syncthreads();
+    rec_mark<RG>(a, b, tid, bits32);
+    __syncthreads();
+    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
+    rec_stage_vecs<RG>(a, b, tid, w, bits16);
+    __syncthreads();
+    const uint32_t total = rec_block_scan(rec_seg_count<RG>(bits16, tid), pre, wtot);
+    if (tid == 0) a.cnt[b] = total;
+    rec_rank_records<RG>(a, b, tid, bits16, pre);
+}
+
+__global__ __launch_bounds__(256) void k_rec_rank(RecArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) rec_add_base(a, RG::TILE, i);
+}
+
+__global__ __launch_bounds__(RG::THREADS) void k_rec_count(RecArgs a) {
+    __shared__ uint32_t wtot[RG::THREADS / kWave];
+    const uint64_t c = wave_sum(rec_count_vecs<RG>(a, blockIdx.x, threadIdx.x, nullptr));
+    if ((threadIdx.x & (kWave - 1)) == 0) wtot[threadIdx.x / kWave] = (uint32_t)c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (int k = 0; k < RG::THREADS / kWave; ++k) t += wtot[k];
+        a.cnt[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(RG::THREADS) void k_rec_locate(RecArgs a, uint32_t* status) {
+    __shared__ uint16_t bits16[RG::NVEC];
+    __shared__ uint32_t pre[RG::THREADS];
+    __shared__ uint32_t wtot[RG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    rec_count_vecs<RG>(a, b, tid, bits16);
+    __syncthreads();
+    const uint32_t total = rec_block_scan(rec_seg_count<RG>(bits16, tid), pre, wtot);
+    const uint32_t bad = wave_or(rec_locate_records<RG>(a, b, tid, bits16, pre, total));
+    if ((tid & (kWave - 1)) == 0 && bad) atomicOr(status, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_rec_restore(RecArgs a, uint8_t* dst) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) rec_restore(a, dst, i);
+}
+
+unsigned rec_grid(int64_t items) {
+    const int64_t blocks = (items + 255) / 256;
+    return (unsigned)(blocks < 1 ? 1 : blocks > 256 * 16 ? 256 * 16 : blocks);
+}
+
+int64_t rec_tile_bytes() { return RG::TILE; }
+void launch_rec_check(const int64_t* off, int64_t nrec, int64_t n, uint32_t* status, void* stream) {
+    hipLaunchKernelGGL(k_rec_check, dim3(rec_grid(nrec + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), off, nrec, n, status);
+}
+void launch_rec_part(int side, const RecArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_rec_part, dim3((unsigned)((tiles + 1 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a, tiles, side);
+}
+void launch_rec_stage(const RecArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_rec_stage, dim3((unsigned)tiles), dim3(RG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_rec_rank(const RecArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_rec_rank, dim3(rec_grid(a.nrec)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_rec_count(const RecArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_rec_count, dim3((unsigned)tiles), dim3(RG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_rec_locate(const RecArgs& a, int64_t tiles, uint32_t* status, void* stream) {
+    hipLaunchKernelGGL(k_rec_locate, dim3((unsigned)tiles), dim3(RG::THREADS), 0, static_cast<hipStream_t>(stream), a, status);
+}
+void launch_rec_restore(const RecArgs& a, uint8_t* dst, void* stream) {
+    hipLaunchKernelGGL(k_rec_restore, dim3(rec_grid(a.nrec)), dim3(256), 0, static_cast<hipStream_t>(stream), a, dst);
 }
 
 }  // namespace trre
