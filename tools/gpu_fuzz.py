@@ -6,7 +6,12 @@ Random patterns (the generator of tests/fuzz_oracle.py over the alphabet abcxy),
 the same alphabet with lines of very different lengths (empty lines, lines longer than a lane's
 sub-range, NULs now and then, with and without a final newline), random buffer sizes and random
 misalignment of the input and output tensors.  --dict P: that share of the patterns are key:value lists of 80..250 keys
-(large stream tables: the comb-packed fallback form)."""
+(large stream tables: the comb-packed fallback form).  --cases N: exactly N patterns instead of a time box (a seed then names ONE run).
+
+--memoryless: the patterns are memoryless programs (gen_memoryless: `b:text` alternatives over the printable bytes, texts of 0..8 bytes, with
+and without a `.:text` catch-all), which the generator above almost never draws; every one runs on the kernel the runtime picks for it
+(TRRE_MAPGEN=1 in the environment: k_mapgen, always) on 1..5 tiles and, with --grid G, on G + 1 tiles.  tests/test_gpu_mapgen_oracle.py runs
+run_memoryless() with a fixed list of seeds."""
 import argparse
 import os
 import random
@@ -85,6 +90,102 @@ def gen_dictionary(rng):
     return b"|".join(k + b":" + bytes(rng.choice(b"xyzXYZ01") for _ in range(rng.randint(0, top))) for k in keys)
 
 
+PLAIN = bytes(c for c in range(0x20, 0x7f) if chr(c) not in ":|*+?()[]{}.\\-,$^I")      # printable bytes the pattern syntax gives no meaning
+
+
+def gen_memoryless(rng):
+    """an alternation of one-byte keys with texts of 0..8 bytes — every attempt is decided by ONE byte: no state —, half of them with a
+    catch-all `.:text` behind it (every byte but the line end prints a text)"""
+    keys = rng.sample(list(PLAIN), rng.choice([1, 1, 2, 3, 5, 8, 13, 26, 40]))
+    top = rng.choice([1, 1, 2, 3, 8, 8])
+    alts = [bytes([k]) + b":" + bytes(rng.choice(PLAIN) for _ in range(rng.randint(0, top))) for k in keys]
+    if all(len(x) == 3 for x in alts):             # (one byte for one byte throughout is a byte map: k_bytemap's, not this kernel's)
+        alts[0] = alts[0][:2] + bytes(rng.choice(PLAIN) for _ in range(rng.choice([0, 2, 3, 8])))
+    pat = b"|".join(alts)
+    if rng.random() < 0.5:
+        pat = b"(" + pat + b")"
+    if rng.random() < 0.5:
+        pat += b"|.:" + bytes(rng.choice(PLAIN) for _ in range(rng.randint(0, rng.choice([1, 2, 8]))))
+    return pat.decode("latin-1")
+
+
+def gen_text(rng, n, keys):
+    """n bytes of lines over the printable bytes, the pattern's keys frequent among them; most lines short, some longer than a 16 KiB tile;
+    no NUL; with and without a final newline"""
+    alpha = bytes(keys) * 3 + PLAIN + b"I:.-"
+    out = bytearray()
+    while len(out) < n:
+        r = rng.random()
+        ln = 0 if r < 0.05 else rng.randint(1, 160) if r < 0.9 else rng.randint(1000, 6000) if r < 0.97 else rng.randint(17000, 40000)
+        line = bytes(rng.choice(alpha) for _ in range(min(ln, 257)))
+        out += (line * (ln // max(len(line), 1) + 1))[:ln] + b"\n"
+    out = bytes(out[:n])
+    if rng.random() < 0.7 and not out.endswith(b"\n"):
+        out = out[:-1] + b"\n"
+    return out
+
+
+def memoryless_programs(pat):
+    """[(engine, oracle, program)] for the engines on which `pat` compiles AND is a memoryless program of the general small-table family (whose
+    one-pass form k_mapgen is): the oracle first — what it refuses is not tried"""
+    progs = []
+    gen = {v: kk for kk, v in trre_amd.KERNEL_NAMES.items()}["stream_gen"]
+    for eng in ("nft", "dft"):
+        try:
+            o = Oracle(pat, eng)
+            p = trre_amd.Program(pat, eng)
+        except (OracleError, trre_amd.TrreError):
+            continue
+        blob = p.export_stream_tables()
+        if gen not in p.allowed_kernels() or not blob or len(blob) < 192 or not int.from_bytes(blob[184:188], "little"):
+            continue                               # (StreamBlobHeader::mg_max == 0: not memoryless; a length-preserving one is a byte map)
+        p.set_kernel(gen)                          # (a long list's own choice may be a guided family)
+        progs.append((eng, o, p))
+    return progs
+
+
+def memoryless_plan(seed, cases):
+    """the `cases` patterns of `seed` with what they are (memoryless_programs): the patterns depend on the seed alone, not on the inputs"""
+    rng = random.Random(seed)
+    return [(pat, memoryless_programs(pat)) for pat in [gen_memoryless(rng) for _ in range(cases)]]
+
+
+def run_memoryless(seed, cases, grid=0, verbose=False):
+    """`cases` patterns drawn from `seed`, each on one input of 1..5 tiles (the first of a seed, with grid: on grid + 1 tiles), both engines
+    where both compile, random alignment of both views, against the oracle.  Every pattern goes through Oracle() first: what it refuses is
+    skipped and counted, and so is a pattern whose program is not memoryless.  Returns (drawn, skipped, scans run, mismatches)."""
+    tile = 16384
+    drawn = skipped = ran = 0
+    bad = []
+    for k, (pat, progs) in enumerate(memoryless_plan(seed, cases)):
+        drawn += 1
+        if not progs:
+            skipped += 1
+            continue
+        rng = random.Random(seed * 1000003 + k)
+        n = (grid + 1) * tile + rng.randint(-20, 20) if grid and k == 0 else rng.randint(1, 5) * tile + rng.choice([-17, -1, 0, 1, 15, rng.randint(-tile + 1, 0)])
+        data = gen_text(rng, n, [ord(a[0]) for a in pat.strip("()").split("|") if a[:1] not in ("", ".", "(", ")")])
+        mis_in, mis_out = rng.choice([0, 1, 7, 8, 15]), rng.choice([0, 1, 15])
+        buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
+        buf[mis_in:mis_in + len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+        for eng, o, p in progs:
+            want = o.scan(data)
+            if verbose:
+                print("case pat=%r eng=%s n=%d mis=(%d,%d)" % (pat, eng, len(data), mis_in, mis_out), flush=True)
+            obuf = torch.full((mis_out + len(want) + 64 + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
+            try:
+                p.enqueue(buf[mis_in:mis_in + len(data)], obuf[mis_out:mis_out + len(want) + 64])
+                m = p.finish()
+                got = obuf[mis_out:mis_out + m].cpu().numpy().tobytes()
+            except trre_amd.TrreError as e:
+                got = ("ERR " + str(e)).encode()
+            ran += 1
+            if got != want or not bool((obuf[mis_out + len(want) + 64:] == 0xA5).all()) or not bool((obuf[:mis_out] == 0xA5).all()):
+                at = next((i for i in range(min(len(got), len(want))) if got[i] != want[i]), min(len(got), len(want)))
+                bad.append("pat=%r eng=%s seed=%d case=%d n=%d mis=(%d,%d) got=%d want=%d first difference at %d" % (pat, eng, seed, k, len(data), mis_in, mis_out, len(got), len(want), at))
+    return drawn, skipped, ran, bad
+
+
 def bounded(fn, data, seconds=20):
     """fn(data) in a forked child, given up after `seconds` (TimeoutError): the reference's backtracking search — and so
     the oracle's — is exponential on some pattern/input pairs, and a C call cannot be interrupted by an alarm.  The child
@@ -131,15 +232,25 @@ def bounded(fn, data, seconds=20):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60)
+    ap.add_argument("--cases", type=int, default=0, help="run exactly this many patterns (no time box): a seed names one run")
+    ap.add_argument("--memoryless", action="store_true", help="memoryless programs only (run_memoryless); needs --cases")
+    ap.add_argument("--grid", type=int, default=0, help="--memoryless: the workgroups of a k_mapgen launch (the first case then has grid + 1 tiles)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verbose", action="store_true", help="print every case before it runs (to find a crashing one)")
     ap.add_argument("--dict", type=float, default=0.03, help="share of patterns that are large key:value lists (fallback form)")
     a = ap.parse_args()
+    if a.memoryless:
+        drawn, skipped, ran, bad = run_memoryless(a.seed, a.cases or 100, a.grid, a.verbose)
+        for b in bad:
+            print("MISMATCH " + b)
+        print("gpu fuzz (memoryless): %d patterns, %d skipped, %d scans, %d mismatches" % (drawn, skipped, ran, len(bad)))
+        return 1 if bad else 0
     rng = random.Random(a.seed)
     t_end = time.time() + a.seconds
-    n_pat = n_run = n_skip = bad = 0
+    n_pat = n_run = n_skip = bad = n_drawn = 0
     fams = {}
-    while time.time() < t_end:
+    while (n_drawn < a.cases) if a.cases else (time.time() < t_end):
+        n_drawn += 1
         if n_pat % 100 == 99:
             print("... %d patterns, %d scans, %d mismatches" % (n_pat, n_run, bad), flush=True)
         r = rng.random()

@@ -157,6 +157,10 @@ __global__ __launch_bounds__(kMapGenThreads, 4) void k_mapgen(ScanArgs a, MapGen
     const MapGenView T{lenp, firstp, textp};
     uint32_t st_all = 0;
     if (tid == 0) misc[12] = misc[14] = 0;
+    // The tables are staged by all 256 threads and looked up by every lane: no lookup before all of them are in.  (Without this barrier a
+    // workgroup whose other waves were late counted its first tile from what the workgroup before it on the CU had left in LDS — as a rule
+    // another program's valid tables —, expanded it from the right ones, and every later place was off: DESIGN.md 4.5c, tools/lds_entry_audit.py.)
+    MG_SYNC();
     const bool prof = oa.prof != nullptr && tid == 0;
     auto stamp = [&](uint64_t& t, int slot) {
         if (prof) {
@@ -271,7 +275,9 @@ __global__ __launch_bounds__(kMapGenThreads, 4) void k_mapgen(ScanArgs a, MapGen
     if (cur < oa.n_tiles) {
         ask(cur, xlo, xhi);
         ask(cur + G, ylo, yhi);
-        st_cur = count_and_publish(cur);                   // (the barrier inside: the tables are staged)
+        st_cur = count_and_publish(cur);                   // (its barrier lies between the waves' totals and their readers — the tables were staged above)
+        MG_SYNC();                                         // (everybody has read misc[0..3]: the first trip's count_and_publish(nxt) stores there, and no
+                                                           // barrier of the first trip lies before it; the later trips end with one)
     } else {
         cur = -1;
     }
