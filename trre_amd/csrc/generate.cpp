@@ -24,6 +24,7 @@
 #include <thread>
 
 #include "front.hpp"
+#include "switches.hpp"
 
 namespace trre {
 namespace {
@@ -78,7 +79,8 @@ GenTables build_gen_tables(const Nft& nft, bool match_mode) {
     }
     g.n_cls = (uint32_t)readers.size();
     // (TRRE_GEN_MAX_REV: a smaller limit, for the tests of the filter that lets everything through)
-    const size_t max_rev = getenv("TRRE_GEN_MAX_REV") ? (size_t)std::max(3, atoi(getenv("TRRE_GEN_MAX_REV"))) : 256;
+    const SwitchNum rev_env = gen_max_rev_now();
+    const size_t max_rev = rev_env.set ? (size_t)std::max(3, (int)rev_env.v) : 256;
     // subset construction, right to left.  States 0..2: nothing viable — inside a line, at its '\n', at a NUL
     std::vector<AnySets> rev(3);
     std::map<std::vector<uint32_t>, uint32_t> rev_index;

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "launch.hpp"
+#include "switches.hpp"
 #include "scan_block.hpp"
 #include "one_block.hpp"
 #include "map_block.hpp"
@@ -412,7 +413,7 @@ int launch_mapgen_t(const ScanArgs& a, const MapGenArgs& oa, hipStream_t s, int 
     }
     const int per_cu = per_cu_cache.load();
     int64_t blocks = (int64_t)cus * per_cu;
-    static const int oversub_env = getenv("TRRE_MAPGEN_OVERSUB") ? atoi(getenv("TRRE_MAPGEN_OVERSUB")) : 0;   // (tests: a grid that is NOT resident — the launch must give up, not hang)
+    const int oversub_env = switches().mapgen_oversub;   // (tests: a grid that is NOT resident — the launch must give up, not hang)
     if (oversub_env > 1) blocks *= oversub_env;
     if (blocks > oa.n_tiles) blocks = oa.n_tiles;
     hipLaunchKernelGGL((k_mapgen<kFirst, kMulti>), dim3((unsigned)blocks), dim3(kMapGenThreads), lds, s, a, oa);

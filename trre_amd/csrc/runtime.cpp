@@ -25,6 +25,7 @@
 #include "device_blob.hpp"
 #include "front.hpp"
 #include "launch.hpp"
+#include "switches.hpp"
 #include "scan_block.hpp"
 #include "splice_block.hpp"
 #include "gen_block.hpp"
@@ -39,10 +40,13 @@ namespace {
 thread_local std::string g_error;
 thread_local uint32_t g_scan_flags = 0;       // TRRE_SCAN_*: what the last scan call on this thread has to add to its return code
 
+constexpr int kNotThisRoute = 1;              // a launch route declines (positive: no TRRE_E_* code): the caller takes the next one
+
 int fail(int code, const std::string& msg) {
     g_error = msg;
     return code;
 }
+int fail_empty(size_t* out_len, int code, const std::string& msg) { if (out_len) *out_len = 0; return fail(code, msg); }     // ... and no output stands
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -96,6 +100,18 @@ void pinned_put(uint8_t* p) {
     ::munmap(p, len);
 }
 
+// What one launch is made of, computed once per enqueue (make_plan): the kernel arguments, the geometry of lanes and chunks, the table forms.
+// finish() keeps it for the rounds it runs on the same launch (the lazy rounds, the repair rounds of the exact sub-ranges).
+struct LaunchPlan {
+    trre::ScanArgs args{};
+    int64_t lane_bytes = 0, rev_lane_bytes = 0, n_chunks = 0;
+    int threads = 0, sym_mode = 0;    // threads: per workgroup of the workspace's owner (ensure_workspace)
+    int g16 = 0;                      // LDS room of the 16-byte + pair forms, 0: the 8-byte entries
+    bool g16_slow = false, direct_ent_lds = false;
+    bool direct = false;              // the stream and guided families: a lane walks a long sub-range straight from memory
+    bool window = false, mapgen_on = false, use_exact = false;    // the window kernel; the memoryless one-pass kernel is to be tried; exact sub-ranges (ScanArgs::exact)
+};
+
 struct Pending {
     bool active = false;
     int family = 0;         // what runs
@@ -113,12 +129,28 @@ struct Pending {
     bool patched = false;                 // the launch was the mark + splice pair of a large table's copy form, not a count / emit pair
     bool one = false;                     // the launch was the one-pass kernel (one_block.hpp), not a count / emit pair
     bool mapgen = false;                  // ... the memoryless one-pass kernel (map_block.hpp)
-    // exact sub-ranges (scan_block.hpp: ScanArgs::exact): what finish() needs to run repair rounds and the emit pass again
-    bool exact = false;
-    trre::ScanArgs xargs{};
-    int64_t x_lane_bytes = 0, x_n_chunks = 0, x_rev_lane_bytes = 0;
-    int x_g16 = 0, x_sym = 0;
-    bool x_slow = false, x_ent_lds = false;
+    bool exact = false;                   // the launch ran exact sub-ranges: finish() runs repair rounds and the emit pass again, from the plan
+    LaunchPlan plan;
+};
+
+// A device buffer that only grows, with its capacity in the units of whoever sizes it.  reserve() leaves pointer = null, capacity = 0 when
+// the allocation fails and hands the error back: the caller chooses what that means (an error, another route, a message of its own).
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    // (moved only — which rules copies out: a ScanCtx is only ever assigned from a fresh one, in ctx_free)
+    DevBuf& operator=(DevBuf&& o) noexcept { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; return *this; }
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t want, size_t bytes) {
+        if (want <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+        if (e != hipSuccess) p = nullptr; else cap = want;
+        return e;
+    }
 };
 
 // Everything ONE in-flight scan needs on a device besides the tables: status words, the workspaces of the
@@ -127,55 +159,37 @@ struct Pending {
 struct ScanCtx {
     uint32_t* d_status = nullptr;     // [4]
     uint32_t* h_status = nullptr;     // pinned mirror: [0] status bits; [2..3] total (u64)
-    uint32_t* d_lane_counts = nullptr;
-    uint64_t* d_chunk_total = nullptr;
-    uint64_t* d_chunk_base = nullptr;
-    int64_t ws_chunks = 0;
-    uint8_t* d_scratch = nullptr;     // NFT tile kernels: mask scratch for lines longer than the LDS tile
-    size_t scratch_bytes = 0;
-    uint32_t* d_redo = nullptr;       // window kernel redo list
-    int64_t redo_lanes = 0;
-    uint8_t* d_sym = nullptr;         // guided families: one symbol per input byte
-    uint8_t* d_snap = nullptr;        // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads;
-    size_t snap_bytes = 0;            // trre_scan_device_records: the staged copy, which the scan reads
-    uint64_t* d_rec = nullptr;        // trre_scan_device_records: status word, then part [tiles + 1], cnt [tiles], base [tiles + 1]
-    int64_t rec_tiles = 0;
-    uint8_t* d_gen_out = nullptr;     // generator modes: the enumeration's output before it goes down
-    size_t gen_out_cap = 0;
-    size_t sym_bytes = 0;
+    DevBuf<uint32_t> d_lane_counts;   // general families' workspace, in chunks of 256 lanes (ensure_workspace) ...
+    DevBuf<uint64_t> d_chunk_total, d_chunk_base;
+    DevBuf<uint8_t> d_scratch;        // NFT tile kernels: mask scratch for lines longer than the LDS tile; the backtracking pool (bytes)
+    DevBuf<uint32_t> d_redo;          // window kernel redo list (lanes)
+    DevBuf<uint8_t> d_sym;            // guided families: one symbol per input byte (bytes)
+    DevBuf<uint8_t> d_snap;           // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads;
+                                      // trre_scan_device_records: the staged copy, which the scan reads (bytes)
+    DevBuf<uint64_t> d_rec;           // trre_scan_device_records: status word, then part [tiles + 1], cnt [tiles], base [tiles + 1] (tiles)
+    DevBuf<uint8_t> d_gen_out;        // generator modes: the enumeration's output before it goes down (bytes)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers
-    uint32_t* d_cevents = nullptr;
-    uint32_t* d_chdr = nullptr;
-    int64_t copy_lanes = 0;
+    // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
+    DevBuf<uint32_t> d_cevents, d_chdr;
     // the stack guard (guard_block.hpp): window flags, runs of flagged windows, results, the pool of stacks, the one line's output
-    uint64_t* d_gflags = nullptr;
-    size_t gflags_words = 0;
-    uint8_t* d_gruns = nullptr;       // GuardRun[gruns_cap], then GuardResult[gruns_cap]
-    size_t gruns_cap = 0;
-    uint32_t* d_gstack = nullptr;     // [kGuardSlots][65 536][3]
-    uint8_t* d_gobuf = nullptr;
-    size_t gobuf_cap = 0;
-    uint8_t* d_gout = nullptr;
-    size_t gout_cap = 0;
+    DevBuf<uint64_t> d_gflags;
+    DevBuf<uint8_t> d_gruns;          // GuardRun[cap], then GuardResult[cap]
+    DevBuf<uint32_t> d_gstack;        // [kGuardSlots][65 536][3]
+    DevBuf<uint8_t> d_gobuf, d_gout;
     // exact sub-ranges: entry / exit states and flags per lane; the long-line probe and what it said about which buffer
-    uint32_t* d_spec = nullptr;
-    int64_t spec_lanes = 0;
-    uint32_t* d_probe = nullptr;
+    DevBuf<uint32_t> d_spec, d_probe;
     const uint8_t* probe_in = nullptr;
     size_t probe_n = 0;
     bool long_lines = false;
     bool exact_off = false;           // finish() runs a scan again the old way (a diverging attempt: the first lane in stream order has to be named)
     // the one-pass kernel (one_block.hpp): look-back descriptors [tiles], then the ticket counter and the total
-    uint64_t* d_one = nullptr;
-    int64_t one_tiles = 0;
+    DevBuf<uint64_t> d_one;
     bool one_off = false;             // finish() runs the scan again as a count / emit pair (a void one-pass launch)
-    uint64_t* d_mg = nullptr;         // the memoryless kernel (map_block.hpp): descriptors, group sums and totals, the total
-    int64_t mg_tiles = 0;
+    DevBuf<uint64_t> d_mg;            // the memoryless kernel (map_block.hpp): descriptors, group sums and totals, the total (tiles)
     bool mapgen_off = false;          // finish() runs the scan again on the general family (a NUL in the input)
     int mapgen_voids = 0;             // launches of the memoryless kernel that were void (a NUL; a grid that was not resident): after two, the pair from the start
     bool mapgen_dense = false;        // a program with longer texts printed 4 % more than it read: its texts are frequent ('a:xyz': the pair is 7 % faster there)
-    uint32_t* d_miss = nullptr;       // lazy tables (lazy_block.hpp): [0] misses listed, then {row, class} pairs
+    DevBuf<uint32_t> d_miss;          // lazy tables (lazy_block.hpp): [0] misses listed, then {row, class} pairs
     int bt_tier = 0;                  // the backtracking fallback: which size of stacks and path buffers the next launch uses (kBtTiers)
     bool guard_off = false;           // finish() scans the lines before a line the guard stopped at: not to be guarded again
     bool patch_off = false;           // finish() runs the scan again as a count / emit pair (diverged, or out of overflow records)
@@ -566,26 +580,9 @@ int ctx_init(ScanCtx& c) {
 void ctx_free(ScanCtx& c) {
     (void)hipFree(c.d_status);
     if (c.h_status) (void)hipHostFree(c.h_status);
-    (void)hipFree(c.d_lane_counts);
-    (void)hipFree(c.d_chunk_total);
-    (void)hipFree(c.d_chunk_base);
-    (void)hipFree(c.d_scratch);
-    (void)hipFree(c.d_redo);
-    (void)hipFree(c.d_sym);
-    (void)hipFree(c.d_snap);
-    (void)hipFree(c.d_rec);
-    (void)hipFree(c.d_gen_out);
-    (void)hipFree(c.d_gflags); (void)hipFree(c.d_gruns); (void)hipFree(c.d_gstack); (void)hipFree(c.d_gobuf); (void)hipFree(c.d_gout);
-    (void)hipFree(c.d_miss);
-    (void)hipFree(c.d_spec);
-    (void)hipFree(c.d_one);
-    (void)hipFree(c.d_mg);
-    (void)hipFree(c.d_probe);
-    (void)hipFree(c.d_cevents);
-    (void)hipFree(c.d_chdr);
     if (c.ev0) (void)hipEventDestroy(c.ev0);
     if (c.ev1) (void)hipEventDestroy(c.ev1);
-    c = ScanCtx();
+    c = ScanCtx();               // (every DevBuf lets go of its memory here)
 }
 
 // the prog's state on device `dev` (tables uploaded on first use); the calling thread's current device must be `dev`
@@ -593,7 +590,7 @@ int device_state(trre_prog* p, int dev, DeviceState** out) {
     std::lock_guard<std::mutex> lock(p->dev_mu);
     auto it = p->dev.find(dev);
     if (it == p->dev.end()) {
-        static const bool trace_on = getenv("TRRE_TRACE") != nullptr;
+        const bool trace_on = trre::switches().trace;
         const auto t0 = std::chrono::steady_clock::now();
         std::unique_ptr<DeviceState> st(new DeviceState);
         st->device = dev;
@@ -618,32 +615,26 @@ int device_state(trre_prog* p, int dev, DeviceState** out) {
     return TRRE_OK;
 }
 
+// the arguments every kernel starts from: the input as 16-byte vectors — its pointer split at the alignment — and the output at the same offset
+trre::ScanArgs base_args(const uint8_t* d_in, size_t n, uint8_t* d_out = nullptr) {
+    const int64_t a = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    trre::ScanArgs args{};
+    args.in_v0 = d_in - a;
+    if (d_out) { args.out_v0 = d_out - a; args.out = d_out; }
+    args.vbeg = a;
+    args.vend = a + (int64_t)n;
+    return args;
+}
+
 int ensure_workspace(ScanCtx* c, int64_t n_chunks, int threads) {
     n_chunks = n_chunks * ((threads + 255) / 256);      // sized in units of 256-lane chunks
-    if (n_chunks <= c->ws_chunks) return TRRE_OK;
-    if (c->d_lane_counts) { (void)hipFree(c->d_lane_counts); (void)hipFree(c->d_chunk_total); (void)hipFree(c->d_chunk_base); }
-    c->d_lane_counts = nullptr; c->d_chunk_total = nullptr; c->d_chunk_base = nullptr;
-    c->ws_chunks = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_lane_counts), (size_t)n_chunks * 256 * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_chunk_total), (size_t)n_chunks * 8));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_chunk_base), (size_t)(n_chunks + 1) * 8));
-    c->ws_chunks = n_chunks;
+    HIP_TRY(c->d_lane_counts.reserve((size_t)n_chunks, (size_t)n_chunks * 256 * 4));
+    HIP_TRY(c->d_chunk_total.reserve((size_t)n_chunks, (size_t)n_chunks * 8));
+    HIP_TRY(c->d_chunk_base.reserve((size_t)n_chunks, (size_t)(n_chunks + 1) * 8));
     return TRRE_OK;
 }
 
 constexpr uint32_t kCopyEvCap = 256;       // events per lane of the copy form (a 2 KiB sub-range of the dictionary corpus holds ~120)
-// (n_lanes counts rows of kCopyEvCap events: a lane of more than 2 KiB takes several)
-int ensure_copy_workspace(ScanCtx* c, int64_t n_lanes) {
-    if (n_lanes <= c->copy_lanes) return TRRE_OK;
-    (void)hipFree(c->d_cevents); (void)hipFree(c->d_chdr);
-    c->d_cevents = nullptr; c->d_chdr = nullptr;
-    c->copy_lanes = 0;
-    // (events: a row of kCopyEvCap per lane, 4 bytes each)
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_cevents), (size_t)n_lanes * kCopyEvCap * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_chdr), (size_t)n_lanes * 16));
-    c->copy_lanes = n_lanes;
-    return TRRE_OK;
-}
 
 // ---- the stack guard (guard_block.hpp) --------------------------------------------------------------------------------
 constexpr int64_t kGuardSlots = 256;                       // lines searched at a time (a stack of 65 536 items each: 192 MiB in all)
@@ -654,9 +645,9 @@ constexpr uint64_t kGuardBudget = 1ull << 23;              // search steps per l
 // leave undecided is SAID: TRRE_SCAN_GUARD_UNDECIDED in trre_last_scan_flags().
 constexpr uint64_t kGuardCallBudget = 1ull << 35;
 constexpr const char* kStackMsg = "error: stack max capacity reached";
+constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
 bool guard_applies(const trre_prog& p, const ScanCtx& cx, size_t n) {
-    static const bool off = getenv("TRRE_NO_STACK_GUARD") != nullptr;
-    return !off && p.guard.on && !cx.guard_off && (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH) && n + 1 >= p.guard.l_min;
+    return !trre::switches().no_stack_guard && p.guard.on && !cx.guard_off && (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH) && n + 1 >= p.guard.l_min;
 }
 struct GuardHit {
     bool hit = false;
@@ -664,12 +655,8 @@ struct GuardHit {
     uint32_t part = 0;         // bytes of the line's output in cx->d_gout, or ~0u: they could not be produced
 };
 template <class T>
-int guard_room(T** d, size_t* have, size_t want) {
-    if (*have >= want) return TRRE_OK;
-    if (*d) (void)hipFree(*d);
-    *d = nullptr; *have = 0;
-    if (hipMalloc(reinterpret_cast<void**>(d), want * sizeof(T)) != hipSuccess) return fail(TRRE_E_TOO_BIG, "error: out of device memory (stack guard)");
-    *have = want;
+int guard_room(DevBuf<T>& d, size_t want) {
+    if (d.reserve(want, want * sizeof(T)) != hipSuccess) return fail(TRRE_E_TOO_BIG, "error: out of device memory (stack guard)");
     return TRRE_OK;
 }
 // Looks for lines long enough to exhaust the reference's stack and runs the reference's search on them.  Synchronous: it ends
@@ -677,14 +664,10 @@ int guard_room(T** d, size_t* have, size_t want) {
 int guard_check(trre_prog* p, DeviceState* st, ScanCtx* cx, const uint8_t* d_in, size_t n, hipStream_t stream, GuardHit* hit) {
     using namespace trre;
     const GuardTables& g = p->guard;
-    const int64_t al = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    ScanArgs args{};
-    args.in_v0 = d_in - al;
-    args.vbeg = al;
-    args.vend = al + (int64_t)n;
+    ScanArgs args = base_args(d_in, n);
     const int64_t n_win = ((int64_t)n + g.window - 1) / g.window;
     const size_t n_words = (size_t)(n_win + 255) / 256 * 4;
-    int rc = guard_room(&cx->d_gflags, &cx->gflags_words, n_words);
+    int rc = guard_room(cx->d_gflags, n_words);
     if (rc) return rc;
     args.blob = st->d_kblob;
     launch_guard_probe(args, g.window, n_win, cx->d_gflags, stream);
@@ -700,7 +683,7 @@ int guard_check(trre_prog* p, DeviceState* st, ScanCtx* cx, const uint8_t* d_in,
     GuardRun* d_runs = nullptr;
     size_t bad = 0;
     bool found = false;
-    static const uint64_t call_budget = getenv("TRRE_GUARD_CALL_BUDGET") ? (uint64_t)atoll(getenv("TRRE_GUARD_CALL_BUDGET")) : kGuardCallBudget;
+    const uint64_t call_budget = (uint64_t)switches().guard_call_budget.or_else((long long)kGuardCallBudget);
     uint64_t steps_spent = 0;
     bool undecided = false;
     for (int64_t w = 0; w < n_win && !found;) {
@@ -721,12 +704,11 @@ int guard_check(trre_prog* p, DeviceState* st, ScanCtx* cx, const uint8_t* d_in,
         }
         if (runs.empty()) break;
         const size_t n_runs = runs.size();
-        rc = guard_room(&cx->d_gruns, &cx->gruns_cap, n_runs * (sizeof(GuardRun) + sizeof(GuardResult)));      // (runs and results share one allocation)
+        rc = guard_room(cx->d_gruns, n_runs * (sizeof(GuardRun) + sizeof(GuardResult)));      // (runs and results share one allocation)
+        if (!rc) rc = guard_room(cx->d_gstack, (size_t)kGuardSlots * kGuardStackMax * 3);     // (allocated once)
         if (rc) return rc;
-        if (!cx->d_gstack && hipMalloc(reinterpret_cast<void**>(&cx->d_gstack), (size_t)kGuardSlots * kGuardStackMax * 12) != hipSuccess)
-            return fail(TRRE_E_TOO_BIG, "error: out of device memory (stack guard)");
-        d_res = reinterpret_cast<GuardResult*>(cx->d_gruns);
-        d_runs = reinterpret_cast<GuardRun*>(cx->d_gruns + n_runs * sizeof(GuardResult));
+        d_res = reinterpret_cast<GuardResult*>(cx->d_gruns.p);
+        d_runs = reinterpret_cast<GuardRun*>(cx->d_gruns.p + n_runs * sizeof(GuardResult));
         HIP_TRY(hipMemcpyAsync(d_runs, runs.data(), n_runs * sizeof(GuardRun), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemsetAsync(d_res, 0, n_runs * sizeof(GuardResult), stream));
         ga = GuardArgs{};
@@ -734,8 +716,7 @@ int guard_check(trre_prog* p, DeviceState* st, ScanCtx* cx, const uint8_t* d_in,
         ga.runs = d_runs;
         ga.results = d_res;
         ga.stack = cx->d_gstack;
-        static const uint64_t budget = getenv("TRRE_GUARD_BUDGET") ? (uint64_t)atoll(getenv("TRRE_GUARD_BUDGET")) : kGuardBudget;
-        ga.budget = budget;
+        ga.budget = (uint64_t)switches().guard_budget.or_else((long long)kGuardBudget);
         ga.obuf = nullptr;                    // (the search alone: PROD writes nothing, FINAL prints nothing)
         ga.obuf_cap = 0xffffffffu;
         launch_guard(false, args, ga, (int64_t)n_runs, kGuardSlots, stream);
@@ -759,13 +740,13 @@ int guard_check(trre_prog* p, DeviceState* st, ScanCtx* cx, const uint8_t* d_in,
     const uint64_t line_len = res[bad].out_len;             // (the search pass leaves the line's length here)
     const uint64_t obuf_want = 16 * (line_len + 1) + 65536, out_want = 16 * (res[bad].bad_at + 1) + 65536;
     if (obuf_want > (1ull << 30) || out_want > (1ull << 30)) return TRRE_OK;
-    if (guard_room(&cx->d_gobuf, &cx->gobuf_cap, (size_t)obuf_want) || guard_room(&cx->d_gout, &cx->gout_cap, (size_t)out_want)) return TRRE_OK;
+    if (guard_room(cx->d_gobuf, (size_t)obuf_want) || guard_room(cx->d_gout, (size_t)out_want)) return TRRE_OK;
     ga.runs = d_runs + bad;
     ga.results = d_res + bad;
     ga.obuf = cx->d_gobuf;
-    ga.obuf_cap = (uint32_t)std::min<uint64_t>(cx->gobuf_cap, 0xfffffff0u);
+    ga.obuf_cap = (uint32_t)std::min<uint64_t>(cx->d_gobuf.cap, 0xfffffff0u);
     ga.out = cx->d_gout;
-    ga.out_cap = cx->gout_cap;
+    ga.out_cap = cx->d_gout.cap;
     launch_guard(true, args, ga, 1, 1, stream);
     HIP_TRY(hipGetLastError());
     GuardResult again{};
@@ -797,8 +778,8 @@ int lazy_ensure(trre_prog* p) {
     if (p->lazy) return TRRE_OK;
     try {
         trre::LazyLimits lim;
-        if (const char* mb = getenv("TRRE_LAZY_MAX_BYTES")) lim.max_bytes = (size_t)atoll(mb);
-        if (const char* ss = getenv("TRRE_LAZY_SEED_STATES")) lim.seed_states = (size_t)atoll(ss);
+        if (const trre::SwitchNum mb = trre::lazy_max_bytes_now(); mb.set) lim.max_bytes = (size_t)mb.v;
+        if (const trre::SwitchNum ss = trre::lazy_seed_states_now(); ss.set) lim.seed_states = (size_t)ss.v;
         p->lazy.reset(new trre::LazyDft(p->dft_nft, lim));
     } catch (const trre::Error& e) {
         return fail(e.code, e.what());
@@ -861,7 +842,7 @@ int lazy_round(trre_prog* p, DeviceState* st, ScanCtx* cx, const trre::ScanArgs&
     using namespace trre;
     int rc = lazy_sync(p, st);
     if (rc) return rc;
-    if (!cx->d_miss) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_miss), (size_t)(2 + trre::kLazyMissWords * kLazyMissCap) * 4));
+    HIP_TRY(cx->d_miss.reserve(1, (size_t)(2 + trre::kLazyMissWords * kLazyMissCap) * 4));       // (allocated once)
     HIP_TRY(hipMemsetAsync(cx->d_miss, 0, 8, stream));
     if (fresh) HIP_TRY(hipMemsetAsync(cx->d_lane_counts, 0xff, (size_t)n_chunks * 256 * 4, stream));
     LazyArgs la{};
@@ -874,8 +855,7 @@ int lazy_round(trre_prog* p, DeviceState* st, ScanCtx* cx, const trre::ScanArgs&
     la.miss_cap = kLazyMissCap;
     static std::atomic<uint32_t> launch_id{0};
     la.gen = ++launch_id;                     // (lazy_block.hpp: marks of other launches — other chunks in flight on the same table — are listed again)
-    static const uint64_t budget = getenv("TRRE_LAZY_BUDGET") ? (uint64_t)atoll(getenv("TRRE_LAZY_BUDGET")) : kLazyBudget;
-    la.budget = budget;
+    la.budget = (uint64_t)switches().lazy_budget.or_else((long long)kLazyBudget);
     launch_lazy(1, args, la, kLazyLaneBytes, n_chunks, stream);
     launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
     launch_lazy(2, args, la, kLazyLaneBytes, n_chunks, stream);
@@ -889,59 +869,338 @@ int lazy_round(trre_prog* p, DeviceState* st, ScanCtx* cx, const trre::ScanArgs&
 struct MapGenChain { std::mutex mu; hipEvent_t ev = nullptr; bool any = false; };
 MapGenChain g_mapgen_chain[64];
 
-// the memoryless kernel's workspace and launch (map_block.hpp); 0: launched (pd.total_at set), else the caller takes another route
-int mapgen_launch(trre_prog* p, ScanCtx* cx, const trre::ScanArgs& args, const trre::StreamTables& stt, hipStream_t stream, Pending& pd) {
+// the memoryless kernel's workspace and launch (map_block.hpp); TRRE_OK: launched (pd.total_at set), else the caller takes another route
+int mapgen_launch(ScanCtx* cx, const trre::ScanArgs& args, const trre::StreamTables& stt, hipStream_t stream, Pending& pd) {
     using namespace trre;
     MapGenArgs oa{};
     oa.n_tiles = (args.vend + kMapGenTile - 1) / kMapGenTile;
     const size_t groups = (size_t)(oa.n_tiles / 64 + 1);
-    static const char* dbg_env = getenv("TRRE_MAPGEN_DBG");                // (a file: every tile's total and place, written by finish())
+    const Switches& sw = switches();
+    const char* dbg_env = sw.mapgen_dbg;
     const size_t words = (size_t)oa.n_tiles + 2 * groups + 1 + 8 + (dbg_env ? 16 * (size_t)oa.n_tiles : 0);   // descriptors, group sums, group totals, the total, phase clocks
-    if (cx->mg_tiles < oa.n_tiles || dbg_env) {
-        if (cx->d_mg) (void)hipFree(cx->d_mg);
-        cx->d_mg = nullptr; cx->mg_tiles = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&cx->d_mg), words * 8) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        cx->mg_tiles = oa.n_tiles;
-    }
+    if (dbg_env) cx->d_mg.release();                 // (a fresh allocation for every launch)
+    if (cx->d_mg.reserve((size_t)oa.n_tiles, words * 8) != hipSuccess) { (void)hipGetLastError(); return kNotThisRoute; }
     oa.desc = cx->d_mg;
     oa.gsum = cx->d_mg + oa.n_tiles;
     oa.ginc = oa.gsum + groups;
     oa.total = oa.ginc + groups;
     // the windows (two: a tile is stored a trip after it was expanded): the whole output of a tile as a rule — 16 KiB of input and an eighth: four
     // workgroups' pairs of windows share a CU's 160 KiB; a tile that prints more takes the clipped path, window by window
-    static const int window_env = getenv("TRRE_MAPGEN_WINDOW") ? atoi(getenv("TRRE_MAPGEN_WINDOW")) : 0;
-    uint32_t window = window_env > 0 ? (uint32_t)window_env : (uint32_t)(kMapGenTile + kMapGenTile / 8);
+    uint32_t window = sw.mapgen_window > 0 ? (uint32_t)sw.mapgen_window : (uint32_t)(kMapGenTile + kMapGenTile / 8);
     oa.window = (window + 15u) & ~15u;
     oa.spin = 1u << 16;
-    if (getenv("TRRE_MAPGEN_NOLB")) oa.spin = 7u;      // (an experiment: no look-back — the pace of the rest; the output is void)
-    static const bool mg_prof = getenv("TRRE_MAPGEN_PROF") != nullptr;       // (phase clocks of the kernel, printed by finish())
-    oa.prof = mg_prof ? oa.total + 1 : nullptr;
+    if (sw.mapgen_nolb) oa.spin = 7u;
+    oa.prof = sw.mapgen_prof ? oa.total + 1 : nullptr;
     oa.dbg = dbg_env ? oa.total + 1 + 8 : nullptr;
     oa.longest = stt.mg_max;
     oa.first_lookup = 0;
     for (int c = 0; c < 256; ++c)
         if ((stt.mg[4 * c + 2] & (15u | kMgNul)) == 1u && (stt.mg[4 * c] & 0xffu) != (uint32_t)c) oa.first_lookup = 1;   // (a NUL voids the launch: whatever it prints)
-    if (hipMemsetAsync(cx->d_mg, 0, words * 8, stream) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    if (hipMemsetAsync(cx->d_mg, 0, words * 8, stream) != hipSuccess) { (void)hipGetLastError(); return kNotThisRoute; }
     {
         int dev = 0;
         (void)hipGetDevice(&dev);
         MapGenChain& ch = g_mapgen_chain[dev & 63];
         std::lock_guard<std::mutex> lk(ch.mu);
-        if (!ch.ev && hipEventCreateWithFlags(&ch.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ch.ev = nullptr; return -1; }
-        if (ch.any && hipStreamWaitEvent(stream, ch.ev, 0) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        if (launch_mapgen(args, oa, stream) != 0) return -1;
-        if (hipEventRecord(ch.ev, stream) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        if (!ch.ev && hipEventCreateWithFlags(&ch.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ch.ev = nullptr; return kNotThisRoute; }
+        if (ch.any && hipStreamWaitEvent(stream, ch.ev, 0) != hipSuccess) { (void)hipGetLastError(); return kNotThisRoute; }
+        if (launch_mapgen(args, oa, stream) != 0) return kNotThisRoute;
+        if (hipEventRecord(ch.ev, stream) != hipSuccess) { (void)hipGetLastError(); return kNotThisRoute; }
         ch.any = true;
     }
     pd.total_at = oa.total;
     pd.mapgen = true;
-    (void)p;
-    return 0;
+    return TRRE_OK;
+}
+
+// Long lines (round 5): is there a sample point without a line end within 32 KiB?  Asked once per buffer (a tiny kernel and a wait), for the
+// families that have the exact sub-ranges to answer with; a length-preserving family then runs as its general sibling (count, exclusive sum,
+// emit: the exact sub-ranges live there).  *family: the family that runs.
+int long_line_switch(trre_prog* p, ScanCtx* cx, int* family, const uint8_t* d_in, size_t n, size_t cap, hipStream_t stream) {
+    const int exact_env = trre::switches().exact;
+    const bool small_tables = (*family == TRRE_KERNEL_STREAM_LP && p->stt.g16_ok) || (*family == TRRE_KERNEL_GUIDED_LP && p->gt.fwd.g16_ok && !p->gt.wide);
+    if (!small_tables || cx->exact_off || exact_env == 0 || cap < n) return TRRE_OK;
+    if (cx->probe_in != d_in || cx->probe_n != n) {
+        HIP_TRY(cx->d_probe.reserve(1, 16));                // (allocated once)
+        uint32_t misses = 0;
+        HIP_TRY(hipMemsetAsync(cx->d_probe, 0, 4, stream));
+        trre::launch_line_probe(base_args(d_in, n), 32768, cx->d_probe, stream);
+        HIP_TRY(hipMemcpyAsync(&misses, cx->d_probe, 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        cx->probe_in = d_in; cx->probe_n = n;
+        cx->long_lines = misses != 0;
+    }
+    if (exact_env == 2 || cx->long_lines)       // (TRRE_EXACT=2: the switch whatever the lines, for A/B runs and tests)
+        *family = *family == TRRE_KERNEL_STREAM_LP ? TRRE_KERNEL_STREAM_GEN : TRRE_KERNEL_GUIDED_GEN;
+    return TRRE_OK;
+}
+
+// the stream-form tables a launch of `family` walks
+const trre::StreamTables& walked_tables(const trre_prog* p, int family) { return is_guided(family) ? p->gt.fwd : p->stt; }
+
+// the launch of `family` over [d_in, d_in + n): arguments, lanes, chunks, table forms.  Touches nothing on the device.
+LaunchPlan make_plan(const trre_prog* p, const DeviceState* st, const ScanCtx* cx, int family, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap) {
+    using namespace trre;
+    const Switches& sw = switches();
+    LaunchPlan pl;
+    ScanArgs& args = pl.args;
+    args = base_args(d_in, n, d_out);
+    args.blob = is_stream(family) ? st->d_sblob : (is_guided(family) ? st->d_gblob : st->d_blob);
+    const StreamTables& stt = walked_tables(p, family);
+    args.status = cx->d_status;
+    args.cap = cap;
+    // a mask scratch left by an earlier, smaller scan must not be used: the kernel asks for one again
+    args.gscratch = cx->d_scratch.cap >= (n + 32) * (size_t)p->mask_bytes ? cx->d_scratch.p : nullptr;
+    const bool backtrack = family == TRRE_KERNEL_BACKTRACK;
+    const bool lazy = family == TRRE_KERNEL_DFT_LAZY;
+    // (the stream and guided families run the direct kernels — a lane walks a long sub-range straight from memory —: their chunks are
+    // counted below, once the sub-range is known.  Rounds 1-5 also kept LDS-tile kernels for the stream tables, TRRE_STREAM_IMPL=0:
+    // 10-100 GB/s, no job since round 2, removed in round 6)
+    const int chunk = backtrack ? (int)kBtLaneBytes * 256 : lazy ? (int)kLazyLaneBytes * 256
+                      : is_stream(family) ? 2048 * direct_block_threads() : chunk_bytes(p->engine, p->mask_bytes);
+    pl.threads = backtrack || lazy ? 256 : is_stream(family) ? direct_block_threads() : block_threads(p->engine, p->mask_bytes);
+    pl.n_chunks = (args.vend + chunk - 1) / chunk;
+    // the positional-window kernel (wave-tiled I/O) for length-preserving tables that have the window form, the direct walkers otherwise
+    pl.window = is_stream(family) && family == TRRE_KERNEL_STREAM_LP && p->stt.lpw_ok &&
+                (reinterpret_cast<uintptr_t>(args.out_v0) & 15u) == 0;   // its 16-byte stores: in and out congruent mod 16 (unaligned they work, at the pace
+                                                                         // of the emit pass alone: 0.94 against 0.98 ms per GiB, round 4)
+    // sub-range per lane: 2 KiB, growing with the input so that about half a million lanes (8192 waves)
+    // walk it — per-lane costs (the skipped head, the tail beyond the sub-range, the wave waiting for its
+    // slowest lane) shrink with longer lanes: cfg 4 at 8 GiB 1.72 TB/s with 2 KiB lanes, 2.06 with 16 KiB
+    int64_t lane_auto = 2048;
+    if (pl.window)
+        while (lane_auto < 16384 && (int64_t)n / (lane_auto * 2) >= 524288) lane_auto *= 2;
+    // (the count / emit pair on the 16-byte entries gains too — 'a:xyz' at 8 GiB: 920 GB/s with 2 KiB lanes, 967 with 8 KiB, 946 with
+    // 32 KiB; ' +: ' 896 / 947 / 805 — and so does the mark + splice pair of a large table, its event lists growing with the sub-range:
+    // cfg 5 at 4 GiB 594 / 663 (4 KiB) / 675; the guided families do not: 647 / 641)
+    // (the guided families' forward passes gain 2 % at 8 GiB, their backward pass loses 15 %: it keeps 2 KiB)
+    if ((family == TRRE_KERNEL_STREAM_GEN && (p->stt.g16_ok || p->stt.fb_ok)) || (is_guided(family) && !p->gt.wide))
+        while (lane_auto < 8192 && (int64_t)n / (lane_auto * 2) >= 262144) lane_auto *= 2;
+    pl.lane_bytes = sw.lane_bytes > 0 ? (sw.lane_bytes + 127) / 128 * 128 : lane_auto;
+    pl.direct = is_stream(family) || is_guided(family);
+    pl.rev_lane_bytes = sw.lane_bytes > 0 ? pl.lane_bytes : 2048;
+    pl.direct_ent_lds = stt.ok && stt.ent.size() * 8 <= (size_t)direct_ent_lds_bytes();
+    pl.g16_slow = (stt.flags & kFlagG16Slow) != 0;
+    pl.g16 = stt.g16_ok && !sw.no_g16 ? (int)(align_up(stt.g16.size() * 4, 16) + stt.p32.size() * 4) : 0;   // LDS room: 16-byte + pair forms
+    // memoryless programs in ONE pass (map_block.hpp) — `[aie]:` in 6.2 ms per 8 GiB where the pair takes 7.6, HTML escapes 8.4 against 11.0.
+    // A program whose longer texts turn out to be frequent (finish(): the output 4 % longer than the input; `a:xyz` on text: 8.6 ms against 8.0)
+    // goes back to the pair for the context's later scans.  TRRE_MAPGEN=1: every memoryless program, always; TRRE_MAPGEN=0: none
+    pl.mapgen_on = stt.mg_max != 0 && (sw.mapgen < 0 ? !(stt.mg_max > 1u && cx->mapgen_dense) : sw.mapgen != 0) && !cx->mapgen_off && cx->mapgen_voids < 2;
+    pl.sym_mode = !is_guided(family) ? 0 : (p->gt.sym_bits == 4 && !sw.no_g16 ? 2 : 1);
+    if (pl.direct) pl.n_chunks = (args.vend + pl.lane_bytes * direct_block_threads() - 1) / (pl.lane_bytes * direct_block_threads());
+    // Exact sub-ranges (round 5): every lane walks the bytes of its sub-range and nothing else, from the state the transducer is in
+    // there — what makes a line of 400 KB as parallel as 4 000 lines of 100 bytes (rounds 1-4: a lane owns the lines that START in its
+    // sub-range and walks them to their end alone, and the backward pass of the guided families has ONE thread carry the state through
+    // a long line: 5.8-9.0 GB/s on such lines; 1 GiB of 400 KB lines now: ' +: ' 6.2 -> 700 GB/s, '(a|b)*c:x' 4.9 -> 520).  On ordinary text the
+    // form costs nothing measurable (1 GiB: 745 against 733 GB/s), so the general families always run it — also what keeps ONE giant line in
+    // a file of short ones from serialising the scan; TRRE_EXACT=0: the old ownership, for A/B runs.
+    pl.use_exact = pl.g16 > 0 && !cx->exact_off && sw.exact != 0 && pl.lane_bytes % 128 == 0 && pl.rev_lane_bytes % 128 == 0 && !is_guided_wide(*p, family);
+    return pl;
+}
+
+// ---- the routes: each queues its kernels on the stream; kNotThisRoute where a route can decline.  enqueue() has set the arguments every
+// family shares and launch_route() where the output size will be; the order of launches, memsets and copies is each route's own.
+
+// tables still being built (lazy_block.hpp): the first round; finish() builds what it missed and runs the next ones
+int route_lazy(trre_prog* p, DeviceState* st, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    return lazy_round(p, st, cx, pl.args, pl.n_chunks, true, stream);
+}
+// the search itself (gen_block.hpp: bt_lane): a pool of workgroups takes the chunks of 256 sub-ranges in turn, each thread
+// with a stack and a path buffer of its own for the whole launch
+int route_backtrack(DeviceState* st, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    const BtTier& tier = kBtTiers[cx->bt_tier];
+    const int64_t pool_blocks = pl.n_chunks < tier.pool_blocks ? pl.n_chunks : tier.pool_blocks;
+    const uint32_t kBtFrames = tier.frames, kBtPathCap = tier.path_cap;
+    const size_t need = (size_t)pool_blocks * 256 * ((size_t)kBtFrames * 16 + kBtPathCap);
+    HIP_TRY(cx->d_scratch.reserve(need, need));
+    GenArgs ga{};
+    ga.stack = reinterpret_cast<uint32_t*>(cx->d_scratch.p);
+    ga.path = cx->d_scratch + (size_t)pool_blocks * 256 * kBtFrames * 16;
+    ga.frames = kBtFrames;
+    ga.path_cap = kBtPathCap;
+    pl.args.blob = st->d_nblob;
+    const uint32_t budget = (uint32_t)switches().bt_budget.or_else(kBtBudget);
+    launch_bt(1, pl.args, ga, kBtLaneBytes, pl.n_chunks, pool_blocks, budget, stream);
+    launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, pl.n_chunks, stream);
+    launch_bt(2, pl.args, ga, kBtLaneBytes, pl.n_chunks, pool_blocks, budget, stream);
+    return TRRE_OK;
+}
+// the positional-window kernel and its redo list
+int route_window(trre_prog* p, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    const int64_t n_lanes = (pl.args.vend + pl.lane_bytes - 1) / pl.lane_bytes;
+    HIP_TRY(cx->d_redo.reserve((size_t)n_lanes, (size_t)(n_lanes + 1) * 4));
+    HIP_TRY(hipMemsetAsync(cx->d_redo, 0, 4, stream));
+    pl.args.redo = cx->d_redo;
+    // (the pair form of the window entries where the tables have it: two input bytes per table read.  TRRE_NO_LPW_PAIR=1: A/B runs)
+    launch_lpw_kernel((int)(p->stt.lpw.size() * 4), p->stt.lpw_delay > 3, pl.direct_ent_lds, pl.args, pl.lane_bytes, stream,
+                      p->stt.lpw2_ok && !switches().no_lpw_pair ? (int)(p->stt.lpw2.size() * 4) : 0);
+    return TRRE_OK;
+}
+// a backward DFA of more than 256 states: 16-bit symbols, both tables through L1 / L2 (scan_block.hpp: wide guided tables)
+int route_wide_guided(ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    launch_rev_wide(pl.args, pl.lane_bytes, stream);
+    launch_wide_fwd(1, pl.args, pl.lane_bytes, pl.n_chunks, stream);
+    launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, pl.n_chunks, stream);
+    launch_wide_fwd(2, pl.args, pl.lane_bytes, pl.n_chunks, stream);
+    return TRRE_OK;
+}
+// length-preserving without a window form: the emit pass alone, every lane writing its lines where it read them
+int route_lp_direct(trre_prog* p, int family, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    if (is_guided(family)) launch_rev_sweep(pl.args, (int)p->gt.n_rev * 256, pl.rev_lane_bytes, stream, pl.sym_mode == 2);
+    pl.args.lp_emit = 1;
+    launch_direct_kernel(2, pl.direct_ent_lds, pl.args, pl.lane_bytes, pl.n_chunks, stream, pl.g16, pl.sym_mode, pl.g16_slow);
+    return TRRE_OK;
+}
+// A large table (a dictionary) in its copy form (default where the tables have it): the comb walk also lists where the replacement texts
+// go, the second pass copies the input around them without walking any table (scan_block.hpp).  TRRE_NO_FB_COPY=1: the count pass + the
+// emit pass on the 8-byte rows (route_large_table_pair), for A/B runs and what finish() falls back to (a NUL in the input, more texts in
+// a sub-range than its event list holds).
+int route_large_table_copy(trre_prog* p, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    const Switches& sw = switches();
+    // (the second pass is the wave-cooperative splice of splice_block.hpp; a table with an escape text longer than its tiles take — more than
+    // 255 bytes — or too large for its LDS has no copy form: the pair)
+    uint32_t esc_max = 0;
+    for (size_t k = 0; k + 3 < p->stt.fb_esc.size(); k += 4) esc_max = std::max(esc_max, p->stt.fb_esc[k + 1]);
+    if (sw.no_fb_copy || sw.fb_emit || cx->patch_off || p->copy_form_off.load() || pl.lane_bytes % 64 != 0 || !fb_copy_fits(p->sblob.data()) ||
+        esc_max > kSpMaxText || !fb_splice_fits(p->sblob.data()))
+        return kNotThisRoute;
+    const int64_t n_lanes = pl.n_chunks * direct_block_threads();
+    const int64_t ev_rows = (pl.lane_bytes + 2047) / 2048;                  // (the event list grows with the sub-range)
+    const size_t rows = (size_t)(n_lanes * ev_rows);                        // (of kCopyEvCap events, 4 bytes each: a lane of more than 2 KiB takes several)
+    HIP_TRY(cx->d_cevents.reserve(rows, rows * kCopyEvCap * 4));
+    HIP_TRY(cx->d_chdr.reserve(rows, rows * 16));
+    FbCopyArgs ca{};
+    ca.events = cx->d_cevents;
+    ca.lane_hdr = cx->d_chdr;
+    ca.ev_cap = kCopyEvCap * (uint32_t)ev_rows;
+    launch_fb_mark(pl.args, ca, p->sblob.data(), pl.lane_bytes, pl.n_chunks, stream);
+    launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, pl.n_chunks, stream);
+    launch_fb_splice(pl.args, ca, p->sblob.data(), pl.lane_bytes, pl.n_chunks, stream);
+    cx->pend.patched = true;
+    return TRRE_OK;
+}
+// A large table in its fallback form: the count pass with every per-byte lookup in LDS (0.86 ms per GiB against 1.62 on the 8-byte rows
+// through L1/L2).  The emit pass over the same form (TRRE_FB_EMIT=1) is correct but slower than the one over the 8-byte rows (3.8 against
+// 2.9 ms): its tables leave LDS for only 512 staging rings per CU.  (TRRE_NO_FB=1 — both passes on the 8-byte rows, for A/B runs — is
+// route_small_pair.)
+int route_large_table_pair(trre_prog* p, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    const bool fb_emit = switches().fb_emit && fb_fits(p->sblob.data());         // (the form next to 512 staging rings)
+    launch_fb_kernel(1, pl.args, p->sblob.data(), pl.lane_bytes, pl.n_chunks, stream);
+    launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, pl.n_chunks, stream);
+    if (fb_emit) launch_fb_kernel(2, pl.args, p->sblob.data(), pl.lane_bytes, pl.n_chunks, stream);
+    else launch_direct_kernel(2, pl.direct_ent_lds, pl.args, pl.lane_bytes, pl.n_chunks, stream, 0, pl.sym_mode, pl.g16_slow);
+    return TRRE_OK;
+}
+// ONE walk (round 6; one_block.hpp — SURVEY.md row f2): lanes of 128 bytes from guessed-and-verified states, a workgroup's whole output
+// staged in LDS, its place in the output by look-back over the workgroups' totals: the input is read once and walked once.  What the
+// kernel cannot answer in place — a lane whose output outgrows its LDS region, a workgroup whose first lane guessed wrong, a replacement
+// text of more than 8 bytes, a wrong guess of the backward pass — voids the launch (kStOneVoid) and finish() runs the pair;
+// after two such launches the program stops trying.
+// MEASURED (profiles/r06_expand_one_*): bit-identical output, 1.05 GiB fetched and 1.06 GiB written per GiB (the pair:
+// 2.2 x that) — and HALF the pair's speed (8 GiB of 'a:xyz': 15.7 ms against 7.9): with a workgroup's output held in LDS only three
+// waves per SIMD are resident, and the walk is a chain of dependent table reads that wants twice that to hide.  So the pair stays
+// the default and this form is opt-in: TRRE_ONE=1.
+int route_one_walk(trre_prog* p, ScanCtx* cx, const trre::StreamTables& stt, const LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    const Switches& sw = switches();
+    if (!pl.use_exact || sw.one != 1 || cx->one_off || p->one_fails.load() >= 2 || stt.max_out > 8u) return kNotThisRoute;
+    OneArgs oa{};
+    oa.lane_bytes = sw.one_lane > 0 ? (uint32_t)((sw.one_lane + 63) / 64 * 64) : 128u;
+    oa.region = sw.one_region > 0 ? (uint32_t)(sw.one_region / 8 * 8 + 4) : 172u;          // (an odd number of dwords)
+    oa.look = sw.one_look > 0 ? (uint32_t)((sw.one_look + 15) / 16 * 16) : 32u;
+    oa.spin = 1u << 20;
+    oa.n_tiles = (pl.args.vend + (int64_t)oa.lane_bytes * kOneThreads - 1) / ((int64_t)oa.lane_bytes * kOneThreads);
+    const size_t words = (size_t)(oa.n_tiles + 2 + 8 + 2 * (oa.n_tiles / 32 + 1));
+    HIP_TRY(cx->d_one.reserve((size_t)oa.n_tiles, words * 8));
+    oa.desc = cx->d_one;
+    oa.ticket = reinterpret_cast<uint32_t*>(cx->d_one + oa.n_tiles);
+    oa.total = cx->d_one + oa.n_tiles + 1;
+    oa.gsum = cx->d_one + oa.n_tiles + 2 + 8;
+    oa.ginc = oa.gsum + (oa.n_tiles / 32 + 1);
+    HIP_TRY(hipMemsetAsync(cx->d_one, 0, words * 8, stream));
+    oa.prof = sw.one_prof ? cx->d_one + oa.n_tiles + 2 : nullptr;
+    ScanArgs wa = pl.args;
+    wa.spec_look = oa.look;                            // (the forward lanes' look-back; the backward pass kept kSpecLook)
+    if (launch_one(wa, oa, stream, (int)align_up(stt.g16.size() * 4, 16), pl.sym_mode, pl.g16_slow) != 0) return kNotThisRoute;      // (the 16-byte form alone: no pair form in LDS)
+    cx->pend.total_at = oa.total;
+    cx->pend.one = true;
+    return TRRE_OK;
+}
+// the count / emit pair of the direct walkers, on exact sub-ranges where the tables have the 16-byte form — or, before it, the one walk
+int route_small_pair(trre_prog* p, ScanCtx* cx, int family, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    ScanArgs& args = pl.args;
+    const int64_t rev_lanes = ((((args.vend + 127) & ~(int64_t)127) + pl.rev_lane_bytes - 1) / pl.rev_lane_bytes + 255) / 256 * 256;
+    if (pl.use_exact) {
+        const int64_t n_lanes = pl.n_chunks * direct_block_threads();
+        const int64_t want = 3 * n_lanes + (is_guided(family) ? 2 * rev_lanes : 0);
+        HIP_TRY(cx->d_spec.reserve((size_t)want, (size_t)want * 4));
+        args.entry_rows = cx->d_spec;
+        args.exit_rows = cx->d_spec + n_lanes;
+        args.spec_flags = cx->d_spec + 2 * n_lanes;
+        args.rev_guess = cx->d_spec + 3 * n_lanes;
+        args.rev_flags = cx->d_spec + 3 * n_lanes + rev_lanes;
+        args.exact = 1;
+        args.spec_look = (uint32_t)kSpecLook;
+    }
+    if (is_guided(family)) {
+        launch_rev_sweep(args, (int)p->gt.n_rev * 256, pl.rev_lane_bytes, stream, pl.sym_mode == 2);
+        if (pl.use_exact) launch_rev_verify(args, pl.rev_lane_bytes, stream, pl.sym_mode == 2);
+    }
+    const int rc = route_one_walk(p, cx, walked_tables(p, family), pl, stream);
+    if (rc != kNotThisRoute) return rc;
+    // (Rounds 3 and 4 had two one-walk forms here — record + patch, and mark + splice for small tables; both lost to this pair and were removed
+    // in round 5: DESIGN.md §4.5.)
+    launch_direct_kernel(1, pl.direct_ent_lds, args, pl.lane_bytes, pl.n_chunks, stream, pl.g16, pl.sym_mode, pl.g16_slow);
+    if (pl.use_exact) launch_spec_verify(args, (args.vend + pl.lane_bytes - 1) / pl.lane_bytes, stream);
+    launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, pl.n_chunks, stream);
+    if (pl.use_exact) args.exact = 2;
+    launch_direct_kernel(2, pl.direct_ent_lds, args, pl.lane_bytes, pl.n_chunks, stream, pl.g16, pl.sym_mode, pl.g16_slow);
+    cx->pend.exact = pl.use_exact;
+    return TRRE_OK;
+}
+// the general stream and guided families: the first of their routes that takes the launch
+int route_direct_general(trre_prog* p, ScanCtx* cx, int family, LaunchPlan& pl, hipStream_t stream) {
+    const trre::StreamTables& stt = walked_tables(p, family);
+    // a MEMORYLESS program (map_block.hpp; round 6): no state, so no walk — lengths, a prefix sum with look-back, the bytes' texts
+    // at their places: ONE pass, one read of the input.  A NUL voids it (finish()).
+    if (family == TRRE_KERNEL_STREAM_GEN && pl.mapgen_on && mapgen_launch(cx, pl.args, stt, stream, cx->pend) == TRRE_OK) return TRRE_OK;
+    if (!is_guided(family) && stt.fb_ok && !trre::switches().no_fb) {
+        const int rc = route_large_table_copy(p, cx, pl, stream);
+        return rc != kNotThisRoute ? rc : route_large_table_pair(p, cx, pl, stream);
+    }
+    return route_small_pair(p, cx, family, pl, stream);
+}
+// the bitmask tile kernels (fallback of last resort)
+int route_tile_pair(trre_prog* p, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) {
+    using namespace trre;
+    launch_tile_kernel(1, p->engine, p->mask_bytes, pl.args, pl.n_chunks, stream);
+    launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, pl.n_chunks, stream);
+    launch_tile_kernel(2, p->engine, p->mask_bytes, pl.args, pl.n_chunks, stream);
+    return TRRE_OK;
+}
+
+int launch_route(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, LaunchPlan& pl, hipStream_t stream) {
+    if (is_gen(family)) cx->pend.total_at = cx->d_chunk_base + pl.n_chunks;      // (count, exclusive sum, emit: the sum's last word; the one-pass kernels have their own)
+    if (family == TRRE_KERNEL_DFT_LAZY) return route_lazy(p, st, cx, pl, stream);
+    if (family == TRRE_KERNEL_BACKTRACK) return route_backtrack(st, cx, pl, stream);
+    if (family == TRRE_KERNEL_BYTEMAP) { pl.args.nul_list = cx->d_status + 4; trre::launch_bytemap(pl.args, stream); return TRRE_OK; }
+    if (family == TRRE_KERNEL_TILE_LP) { trre::launch_tile_kernel(0, p->engine, p->mask_bytes, pl.args, pl.n_chunks, stream); return TRRE_OK; }
+    if (pl.window) return route_window(p, cx, pl, stream);
+    if (is_guided(family) && p->gt.wide) return route_wide_guided(cx, pl, stream);
+    if (pl.direct && !is_gen(family)) return route_lp_direct(p, family, pl, stream);
+    if (pl.direct) return route_direct_general(p, cx, family, pl, stream);
+    return route_tile_pair(p, cx, pl, stream);
 }
 
 int enqueue(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap,
             hipStream_t stream) {
-    using namespace trre;
     Pending& pd = cx->pend;
     // Back-to-back enqueues without a finish() in between form one batch: status bits accumulate, the
     // timing events bracket the whole batch and finish() speaks for the last launch — so every launch of
@@ -959,12 +1218,7 @@ int enqueue(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, const uint8_
     if (aliased) {
         const size_t a0 = reinterpret_cast<uintptr_t>(d_in) & 15u;
         if (!batch) {
-            if (cx->snap_bytes < n + 16) {
-                if (cx->d_snap) (void)hipFree(cx->d_snap);
-                cx->d_snap = nullptr; cx->snap_bytes = 0;
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_snap), n + 16));
-                cx->snap_bytes = n + 16;
-            }
+            HIP_TRY(cx->d_snap.reserve(n + 16, n + 16));
             HIP_TRY(hipMemcpyAsync(cx->d_snap + a0, d_in, n, hipMemcpyDeviceToDevice, stream));
         }
         d_in = cx->d_snap + a0;
@@ -976,318 +1230,37 @@ int enqueue(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, const uint8_
     pd.d_in = d_in; pd.d_out = d_out; pd.n = n; pd.cap = cap; pd.stream = stream;
     pd.user_in = user_in; pd.aliased = aliased;
     if (n == 0) return TRRE_OK;
-    int rc;
-    // Long lines (round 5): is there a sample point without a line end within 32 KiB?  Asked once per buffer (a tiny kernel and a wait), for the
-    // families that have the exact sub-ranges to answer with; a length-preserving family then runs as its general sibling (count, exclusive sum,
-    // emit: the exact sub-ranges live there).
-    static const int exact_env0 = getenv("TRRE_EXACT") ? atoi(getenv("TRRE_EXACT")) : -1;
-    {
-        const bool small_tables = (family == TRRE_KERNEL_STREAM_LP && p->stt.g16_ok) || (family == TRRE_KERNEL_GUIDED_LP && p->gt.fwd.g16_ok && !p->gt.wide);
-        if (small_tables && !cx->exact_off && exact_env0 != 0 && cap >= n) {
-            if (cx->probe_in != d_in || cx->probe_n != n) {
-                const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-                ScanArgs pa{};
-                pa.in_v0 = d_in - a0; pa.vbeg = a0; pa.vend = a0 + (int64_t)n;
-                if (!cx->d_probe) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_probe), 16));
-                uint32_t misses = 0;
-                HIP_TRY(hipMemsetAsync(cx->d_probe, 0, 4, stream));
-                launch_line_probe(pa, 32768, cx->d_probe, stream);
-                HIP_TRY(hipMemcpyAsync(&misses, cx->d_probe, 4, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                cx->probe_in = d_in; cx->probe_n = n;
-                cx->long_lines = misses != 0;
-            }
-            const bool longl = exact_env0 == 2 || cx->long_lines;       // (TRRE_EXACT=2: the switch whatever the lines, for A/B runs and tests)
-            if (longl) {
-                family = family == TRRE_KERNEL_STREAM_LP ? TRRE_KERNEL_STREAM_GEN : TRRE_KERNEL_GUIDED_GEN;
-                pd.family = family;
-            }
-        }
-    }
-
-    const int64_t a = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    ScanArgs args{};
-    args.in_v0 = d_in - a;
-    args.out_v0 = d_out - a;
-    args.out = d_out;
-    args.vbeg = a;
-    args.vend = a + (int64_t)n;
-    args.blob = is_stream(family) ? st->d_sblob : (is_guided(family) ? st->d_gblob : st->d_blob);
-    const trre::StreamTables& stt = is_guided(family) ? p->gt.fwd : p->stt;       // the stream-form tables this launch walks
-    args.status = cx->d_status;
-    args.cap = cap;
-    // a mask scratch left by an earlier, smaller scan must not be used: the kernel asks for one again
-    args.gscratch = cx->scratch_bytes >= (n + 32) * (size_t)p->mask_bytes ? cx->d_scratch : nullptr;
-    const bool backtrack = family == TRRE_KERNEL_BACKTRACK;
-    const bool lazy = family == TRRE_KERNEL_DFT_LAZY;
-    if (lazy) { rc = lazy_ensure(p); if (rc) return rc; }
-    // (the stream and guided families run the direct kernels — a lane walks a long sub-range straight from memory —: their chunks are
-    // counted below, once the sub-range is known.  Rounds 1-5 also kept LDS-tile kernels for the stream tables, TRRE_STREAM_IMPL=0:
-    // 10-100 GB/s, no job since round 2, removed in round 6)
-    const int chunk = backtrack ? (int)kBtLaneBytes * 256 : lazy ? (int)kLazyLaneBytes * 256
-                      : is_stream(family) ? 2048 * direct_block_threads() : chunk_bytes(p->engine, p->mask_bytes);
-    const int threads = backtrack || lazy ? 256 : is_stream(family) ? direct_block_threads() : block_threads(p->engine, p->mask_bytes);
-    int64_t n_chunks = (args.vend + chunk - 1) / chunk;
-    static const int64_t lane_bytes_env = getenv("TRRE_LANE_BYTES") ? atoll(getenv("TRRE_LANE_BYTES")) : 0;
-    // the positional-window kernel (wave-tiled I/O) for length-preserving tables that have the window form, the direct walkers otherwise
-    const bool window = is_stream(family) && family == TRRE_KERNEL_STREAM_LP && p->stt.lpw_ok &&
-                        (reinterpret_cast<uintptr_t>(args.out_v0) & 15u) == 0;   // its 16-byte stores: in and out congruent mod 16 (unaligned they work, at the pace
-                                                                                 // of the emit pass alone: 0.94 against 0.98 ms per GiB, round 4)
-    // sub-range per lane: 2 KiB, growing with the input so that about half a million lanes (8192 waves)
-    // walk it — per-lane costs (the skipped head, the tail beyond the sub-range, the wave waiting for its
-    // slowest lane) shrink with longer lanes: cfg 4 at 8 GiB 1.72 TB/s with 2 KiB lanes, 2.06 with 16 KiB
-    int64_t lane_auto = 2048;
-    if (window)
-        while (lane_auto < 16384 && (int64_t)n / (lane_auto * 2) >= 524288) lane_auto *= 2;
-    // (the count / emit pair on the 16-byte entries gains too — 'a:xyz' at 8 GiB: 920 GB/s with 2 KiB lanes, 967 with 8 KiB, 946 with
-    // 32 KiB; ' +: ' 896 / 947 / 805 — and so does the mark + splice pair of a large table, its event lists growing with the sub-range:
-    // cfg 5 at 4 GiB 594 / 663 (4 KiB) / 675; the guided families do not: 647 / 641)
-    // (the guided families' forward passes gain 2 % at 8 GiB, their backward pass loses 15 %: it keeps 2 KiB)
-    if ((family == TRRE_KERNEL_STREAM_GEN && (p->stt.g16_ok || p->stt.fb_ok)) || (is_guided(family) && !p->gt.wide))
-        while (lane_auto < 8192 && (int64_t)n / (lane_auto * 2) >= 262144) lane_auto *= 2;
-    const int64_t lane_bytes = lane_bytes_env > 0 ? (lane_bytes_env + 127) / 128 * 128 : lane_auto;
-    const bool direct = is_stream(family) || is_guided(family);
-    const int64_t rev_lane_bytes = lane_bytes_env > 0 ? lane_bytes : 2048;
-    const bool direct_ent_lds = stt.ok && stt.ent.size() * 8 <= (size_t)direct_ent_lds_bytes();
-    const bool g16_slow = (stt.flags & kFlagG16Slow) != 0;
-    static const bool no_g16_env = getenv("TRRE_NO_G16") != nullptr;       // A/B: the 8-byte entries
-    static const bool no_fb_env = getenv("TRRE_NO_FB") != nullptr;         // A/B: large tables walk their 8-byte rows in both passes
-    // memoryless programs in ONE pass (map_block.hpp) — `[aie]:` in 6.2 ms per 8 GiB where the pair takes 7.6, HTML escapes 8.4 against 11.0.
-    // A program whose longer texts turn out to be frequent (finish(): the output 4 % longer than the input; `a:xyz` on text: 8.6 ms against 8.0)
-    // goes back to the pair for the context's later scans.  TRRE_MAPGEN=1: every memoryless program, always; TRRE_MAPGEN=0: none
-    static const int mapgen_env = getenv("TRRE_MAPGEN") ? atoi(getenv("TRRE_MAPGEN")) : -1;
-    const bool mapgen_on = stt.mg_max != 0 && (mapgen_env < 0 ? !(stt.mg_max > 1u && cx->mapgen_dense) : mapgen_env != 0) && !cx->mapgen_off && cx->mapgen_voids < 2;
-    const int sym_mode = !is_guided(family) ? 0 : (p->gt.sym_bits == 4 && !no_g16_env ? 2 : 1);
-    if (direct) n_chunks = (args.vend + lane_bytes * direct_block_threads() - 1) / (lane_bytes * direct_block_threads());
-
+    int rc = long_line_switch(p, cx, &family, d_in, n, cap, stream);
+    if (rc) return rc;
+    pd.family = family;
+    if (family == TRRE_KERNEL_DFT_LAZY) { rc = lazy_ensure(p); if (rc) return rc; }
+    LaunchPlan pl = make_plan(p, st, cx, family, d_in, n, d_out, cap);
     if (!is_gen(family) && cap < n) return TRRE_OK;   // finish() reports the capacity error
     if (is_gen(family)) {
-        rc = ensure_workspace(cx, n_chunks, direct ? direct_block_threads() : threads);
+        rc = ensure_workspace(cx, pl.n_chunks, pl.direct ? trre::direct_block_threads() : pl.threads);
         if (rc) return rc;
-        args.lane_counts = cx->d_lane_counts;
-        args.chunk_total = cx->d_chunk_total;
-        args.chunk_base = cx->d_chunk_base;
+        pl.args.lane_counts = cx->d_lane_counts;
+        pl.args.chunk_total = cx->d_chunk_total;
+        pl.args.chunk_base = cx->d_chunk_base;
     }
     if (is_guided(family)) {
         // one symbol per input byte, written by the backward pass (whole 64-byte pieces) and read by the forward pass
-        const size_t need = ((size_t)((args.vend + 63) & ~(int64_t)63) + 256) * (p->gt.wide ? 2 : 1);
-        if (cx->sym_bytes < need) {
-            if (cx->d_sym) (void)hipFree(cx->d_sym);
-            cx->d_sym = nullptr; cx->sym_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_sym), need));
-            cx->sym_bytes = need;
-        }
-        args.rblob = st->d_rblob;
-        args.sym_v0 = cx->d_sym;
+        const size_t need = ((size_t)((pl.args.vend + 63) & ~(int64_t)63) + 256) * (p->gt.wide ? 2 : 1);
+        HIP_TRY(cx->d_sym.reserve(need, need));
+        pl.args.rblob = st->d_rblob;
+        pl.args.sym_v0 = cx->d_sym;
     }
     if (!batch) {
         HIP_TRY(hipMemsetAsync(cx->d_status, 0, 24, stream));          // (status words and the NUL count)
         if (p->profiling) HIP_TRY(hipEventRecord(cx->ev0, stream));
     }
     pd.timed = p->profiling;
-    if (lazy) {
-        // tables still being built (lazy_block.hpp): the first round; finish() builds what it missed and runs the next ones
-        rc = lazy_round(p, st, cx, args, n_chunks, true, stream);
-        if (rc) return rc;
-        pd.total_at = cx->d_chunk_base + n_chunks;
-    } else if (backtrack) {
-        // the search itself (gen_block.hpp: bt_lane): a pool of workgroups takes the chunks of 256 sub-ranges in turn, each thread
-        // with a stack and a path buffer of its own for the whole launch
-        const BtTier& tier = kBtTiers[cx->bt_tier];
-        const int64_t pool_blocks = n_chunks < tier.pool_blocks ? n_chunks : tier.pool_blocks;
-        const uint32_t kBtFrames = tier.frames, kBtPathCap = tier.path_cap;
-        const size_t need = (size_t)pool_blocks * 256 * ((size_t)kBtFrames * 16 + kBtPathCap);
-        if (cx->scratch_bytes < need) {
-            if (cx->d_scratch) (void)hipFree(cx->d_scratch);
-            cx->d_scratch = nullptr; cx->scratch_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_scratch), need));
-            cx->scratch_bytes = need;
-        }
-        GenArgs ga{};
-        ga.stack = reinterpret_cast<uint32_t*>(cx->d_scratch);
-        ga.path = cx->d_scratch + (size_t)pool_blocks * 256 * kBtFrames * 16;
-        ga.frames = kBtFrames;
-        ga.path_cap = kBtPathCap;
-        args.blob = st->d_nblob;
-        static const uint32_t budget = getenv("TRRE_BT_BUDGET") ? (uint32_t)atoll(getenv("TRRE_BT_BUDGET")) : kBtBudget;
-        launch_bt(1, args, ga, kBtLaneBytes, n_chunks, pool_blocks, budget, stream);
-        launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
-        launch_bt(2, args, ga, kBtLaneBytes, n_chunks, pool_blocks, budget, stream);
-        pd.total_at = cx->d_chunk_base + n_chunks;
-    } else if (family == TRRE_KERNEL_BYTEMAP) {
-        args.nul_list = cx->d_status + 4;
-        launch_bytemap(args, stream);
-    } else if (family == TRRE_KERNEL_TILE_LP) {
-        launch_tile_kernel(0, p->engine, p->mask_bytes, args, n_chunks, stream);
-    } else if (window) {
-        const int64_t n_lanes = (args.vend + lane_bytes - 1) / lane_bytes;
-        if (cx->redo_lanes < n_lanes) {
-            if (cx->d_redo) (void)hipFree(cx->d_redo);
-            cx->d_redo = nullptr; cx->redo_lanes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_redo), (size_t)(n_lanes + 1) * 4));
-            cx->redo_lanes = n_lanes;
-        }
-        HIP_TRY(hipMemsetAsync(cx->d_redo, 0, 4, stream));
-        args.redo = cx->d_redo;
-        // (the pair form of the window entries where the tables have it: two input bytes per table read.  TRRE_NO_LPW_PAIR=1: A/B runs)
-        static const bool no_pair_env = getenv("TRRE_NO_LPW_PAIR") != nullptr;
-        launch_lpw_kernel((int)(p->stt.lpw.size() * 4), p->stt.lpw_delay > 3, direct_ent_lds, args, lane_bytes, stream,
-                          p->stt.lpw2_ok && !no_pair_env ? (int)(p->stt.lpw2.size() * 4) : 0);
-    } else if (is_guided(family) && p->gt.wide) {
-        // a backward DFA of more than 256 states: 16-bit symbols, both tables through L1 / L2 (scan_block.hpp: wide guided tables)
-        launch_rev_wide(args, lane_bytes, stream);
-        launch_wide_fwd(1, args, lane_bytes, n_chunks, stream);
-        launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
-        launch_wide_fwd(2, args, lane_bytes, n_chunks, stream);
-        pd.total_at = cx->d_chunk_base + n_chunks;
-    } else if (direct && !is_gen(family)) {
-        // length-preserving without a window form: the emit pass alone, every lane writing its lines where it read them
-        const int g16 = stt.g16_ok && !no_g16_env ? (int)(align_up(stt.g16.size() * 4, 16) + stt.p32.size() * 4) : 0;   // LDS room: 16-byte + pair forms
-        if (is_guided(family)) launch_rev_sweep(args, (int)p->gt.n_rev * 256, rev_lane_bytes, stream, sym_mode == 2);
-        args.lp_emit = 1;
-        launch_direct_kernel(2, direct_ent_lds, args, lane_bytes, n_chunks, stream, g16, sym_mode, g16_slow);
-    } else if (direct && family == TRRE_KERNEL_STREAM_GEN && mapgen_on &&
-               mapgen_launch(p, cx, args, stt, stream, pd) == 0) {
-        // a MEMORYLESS program (map_block.hpp; round 6): no state, so no walk — lengths, a prefix sum with look-back, the bytes' texts
-        // at their places: ONE pass, one read of the input.  A NUL voids it (finish()).
-    } else if (direct && !is_guided(family) && stt.fb_ok && !no_fb_env) {
-        // a large table (a dictionary) in its fallback form: the count pass with every per-byte lookup in LDS (0.86 ms per
-        // GiB against 1.62 on the 8-byte rows through L1/L2).  The emit pass over the same form (TRRE_FB_EMIT=1) is
-        // correct but slower than the one over the 8-byte rows (3.8 against 2.9 ms): its tables leave LDS for only 512
-        // staging rings per CU.  TRRE_NO_FB=1: both passes on the 8-byte rows, for A/B runs.
-        static const bool fb_emit_env = getenv("TRRE_FB_EMIT") != nullptr;
-        const bool fb_emit = fb_emit_env && fb_fits(p->sblob.data());         // (the form next to 512 staging rings)
-        // The copy form (default where the tables have it): the comb walk also lists where the replacement texts go, the
-        // second pass copies the input around them without walking any table (scan_block.hpp).  TRRE_NO_FB_COPY=1: the
-        // count pass + the emit pass on the 8-byte rows, for A/B runs and what finish() falls back to (a NUL in the input,
-        // more texts in a sub-range than its event list holds).
-        static const bool no_copy_env = getenv("TRRE_NO_FB_COPY") != nullptr;
-        // (the second pass is the wave-cooperative splice of splice_block.hpp; a table with an escape text longer than its tiles take — more than
-        // 255 bytes — or too large for its LDS has no copy form: the pair below)
-        uint32_t esc_max = 0;
-        for (size_t k = 0; k + 3 < p->stt.fb_esc.size(); k += 4) esc_max = std::max(esc_max, p->stt.fb_esc[k + 1]);
-        if (!no_copy_env && !fb_emit_env && !cx->patch_off && !p->copy_form_off.load() && lane_bytes % 64 == 0 && fb_copy_fits(p->sblob.data()) &&
-            esc_max <= kSpMaxText && fb_splice_fits(p->sblob.data())) {
-            const int64_t n_lanes = n_chunks * direct_block_threads();
-            const int64_t ev_rows = (lane_bytes + 2047) / 2048;                  // (the event list grows with the sub-range)
-            rc = ensure_copy_workspace(cx, n_lanes * ev_rows);
-            if (rc) return rc;
-            FbCopyArgs ca{};
-            ca.events = cx->d_cevents;
-            ca.lane_hdr = cx->d_chdr;
-            ca.ev_cap = kCopyEvCap * (uint32_t)ev_rows;
-            launch_fb_mark(args, ca, p->sblob.data(), lane_bytes, n_chunks, stream);
-            launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
-            launch_fb_splice(args, ca, p->sblob.data(), lane_bytes, n_chunks, stream);
-            pd.total_at = cx->d_chunk_base + n_chunks;
-            pd.patched = true;
-        } else {
-        launch_fb_kernel(1, args, p->sblob.data(), lane_bytes, n_chunks, stream);
-        launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
-        if (fb_emit) launch_fb_kernel(2, args, p->sblob.data(), lane_bytes, n_chunks, stream);
-        else launch_direct_kernel(2, direct_ent_lds, args, lane_bytes, n_chunks, stream, 0, sym_mode, g16_slow);
-        pd.total_at = cx->d_chunk_base + n_chunks;
-        }
-    } else if (direct) {
-        const int g16 = stt.g16_ok && !no_g16_env ? (int)(align_up(stt.g16.size() * 4, 16) + stt.p32.size() * 4) : 0;   // LDS room: 16-byte + pair forms
-        // Exact sub-ranges (round 5): every lane walks the bytes of its sub-range and nothing else, from the state the transducer is in
-        // there — what makes a line of 400 KB as parallel as 4 000 lines of 100 bytes (rounds 1-4: a lane owns the lines that START in its
-        // sub-range and walks them to their end alone, and the backward pass of the guided families has ONE thread carry the state through
-        // a long line: 5.8-9.0 GB/s on such lines; 1 GiB of 400 KB lines now: ' +: ' 6.2 -> 700 GB/s, '(a|b)*c:x' 4.9 -> 520).  On ordinary text the
-        // form costs nothing measurable (1 GiB: 745 against 733 GB/s), so the general families always run it — also what keeps ONE giant line in
-        // a file of short ones from serialising the scan; TRRE_EXACT=0: the old ownership, for A/B runs.
-        static const int exact_env = getenv("TRRE_EXACT") ? atoi(getenv("TRRE_EXACT")) : -1;
-        bool use_exact = g16 > 0 && !cx->exact_off && exact_env != 0 && lane_bytes % 128 == 0 && rev_lane_bytes % 128 == 0 &&
-                         !is_guided_wide(*p, family);
-        const int64_t rev_lanes = ((((args.vend + 127) & ~(int64_t)127) + rev_lane_bytes - 1) / rev_lane_bytes + 255) / 256 * 256;
-        if (use_exact) {
-            const int64_t n_lanes = n_chunks * direct_block_threads();
-            const int64_t want = 3 * n_lanes + (is_guided(family) ? 2 * rev_lanes : 0);
-            if (cx->spec_lanes < want) {
-                if (cx->d_spec) (void)hipFree(cx->d_spec);
-                cx->d_spec = nullptr; cx->spec_lanes = 0;
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_spec), (size_t)want * 4));
-                cx->spec_lanes = want;
-            }
-            args.entry_rows = cx->d_spec;
-            args.exit_rows = cx->d_spec + n_lanes;
-            args.spec_flags = cx->d_spec + 2 * n_lanes;
-            args.rev_guess = cx->d_spec + 3 * n_lanes;
-            args.rev_flags = cx->d_spec + 3 * n_lanes + rev_lanes;
-            args.exact = 1;
-            args.spec_look = (uint32_t)kSpecLook;
-        }
-        if (is_guided(family)) {
-            launch_rev_sweep(args, (int)p->gt.n_rev * 256, rev_lane_bytes, stream, sym_mode == 2);
-            if (use_exact) launch_rev_verify(args, rev_lane_bytes, stream, sym_mode == 2);
-        }
-        // ONE walk (round 6; one_block.hpp — SURVEY.md row f2): lanes of 128 bytes from guessed-and-verified states, a workgroup's whole output
-        // staged in LDS, its place in the output by look-back over the workgroups' totals: the input is read once and walked once.  What the
-        // kernel cannot answer in place — a lane whose output outgrows its LDS region, a workgroup whose first lane guessed wrong, a replacement
-        // text of more than 8 bytes, a wrong guess of the backward pass — voids the launch (kStOneVoid) and finish() runs the pair below;
-        // after two such launches the program stops trying.
-        // MEASURED (profiles/r06_expand_one_*): bit-identical output, 1.05 GiB fetched and 1.06 GiB written per GiB (the pair:
-        // 2.2 x that) — and HALF the pair's speed (8 GiB of 'a:xyz': 15.7 ms against 7.9): with a workgroup's output held in LDS only three
-        // waves per SIMD are resident, and the walk is a chain of dependent table reads that wants twice that to hide.  So the pair stays
-        // the default and this form is opt-in: TRRE_ONE=1.
-        static const int one_env = getenv("TRRE_ONE") ? atoi(getenv("TRRE_ONE")) : 0;
-        static const int one_lane_env = getenv("TRRE_ONE_LANE") ? atoi(getenv("TRRE_ONE_LANE")) : 0;
-        static const int one_region_env = getenv("TRRE_ONE_REGION") ? atoi(getenv("TRRE_ONE_REGION")) : 0;
-        static const int one_look_env = getenv("TRRE_ONE_LOOK") ? atoi(getenv("TRRE_ONE_LOOK")) : 0;
-        if (use_exact && one_env == 1 && !cx->one_off && p->one_fails.load() < 2 && stt.max_out <= 8u) {
-            OneArgs oa{};
-            oa.lane_bytes = one_lane_env > 0 ? (uint32_t)((one_lane_env + 63) / 64 * 64) : 128u;
-            oa.region = one_region_env > 0 ? (uint32_t)(one_region_env / 8 * 8 + 4) : 172u;          // (an odd number of dwords)
-            oa.look = one_look_env > 0 ? (uint32_t)((one_look_env + 15) / 16 * 16) : 32u;
-            oa.spin = 1u << 20;
-            oa.n_tiles = (args.vend + (int64_t)oa.lane_bytes * kOneThreads - 1) / ((int64_t)oa.lane_bytes * kOneThreads);
-            if (cx->one_tiles < oa.n_tiles) {
-                if (cx->d_one) (void)hipFree(cx->d_one);
-                cx->d_one = nullptr; cx->one_tiles = 0;
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_one), (size_t)(oa.n_tiles + 2 + 8 + 2 * (oa.n_tiles / 32 + 1)) * 8));
-                cx->one_tiles = oa.n_tiles;
-            }
-            oa.desc = cx->d_one;
-            oa.ticket = reinterpret_cast<uint32_t*>(cx->d_one + oa.n_tiles);
-            oa.total = cx->d_one + oa.n_tiles + 1;
-            oa.gsum = cx->d_one + oa.n_tiles + 2 + 8;
-            oa.ginc = oa.gsum + (oa.n_tiles / 32 + 1);
-            HIP_TRY(hipMemsetAsync(cx->d_one, 0, (size_t)(oa.n_tiles + 2 + 8 + 2 * (oa.n_tiles / 32 + 1)) * 8, stream));
-            static const bool one_prof = getenv("TRRE_ONE_PROF") != nullptr;        // (phase clocks of the kernel, printed by finish())
-            oa.prof = one_prof ? cx->d_one + oa.n_tiles + 2 : nullptr;
-            ScanArgs wa = args;
-            wa.spec_look = oa.look;                            // (the forward lanes' look-back; the backward pass above kept kSpecLook)
-            if (launch_one(wa, oa, stream, (int)align_up(stt.g16.size() * 4, 16), sym_mode, g16_slow) == 0) {      // (the 16-byte form alone: no pair form in LDS)
-                pd.total_at = oa.total;
-                pd.one = true;
-                HIP_TRY(hipGetLastError());
-                pd.launched = true;
-                pd.count += 1;
-                return TRRE_OK;
-            }
-        }
-        // (Rounds 3 and 4 had two one-walk forms here — record + patch, and mark + splice for small tables; both lost to this pair and were removed
-        // in round 5: DESIGN.md §4.5.)
-        launch_direct_kernel(1, direct_ent_lds, args, lane_bytes, n_chunks, stream, g16, sym_mode, g16_slow);
-        if (use_exact) launch_spec_verify(args, (args.vend + lane_bytes - 1) / lane_bytes, stream);
-        launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
-        if (use_exact) args.exact = 2;
-        launch_direct_kernel(2, direct_ent_lds, args, lane_bytes, n_chunks, stream, g16, sym_mode, g16_slow);
-        pd.total_at = cx->d_chunk_base + n_chunks;
-        if (use_exact) {
-            pd.exact = true;
-            pd.xargs = args; pd.x_lane_bytes = lane_bytes; pd.x_n_chunks = n_chunks; pd.x_g16 = g16; pd.x_sym = sym_mode; pd.x_slow = g16_slow; pd.x_ent_lds = direct_ent_lds;
-            pd.x_rev_lane_bytes = is_guided(family) ? rev_lane_bytes : 0;
-        }
-    } else {
-        launch_tile_kernel(1, p->engine, p->mask_bytes, args, n_chunks, stream);
-        launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, n_chunks, stream);
-        launch_tile_kernel(2, p->engine, p->mask_bytes, args, n_chunks, stream);
-        pd.total_at = cx->d_chunk_base + n_chunks;
-    }
+    rc = launch_route(p, st, cx, family, pl, stream);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     // (the status word, the output size and the closing timing event are fetched by finish(): nothing
     // sits between the kernels of back-to-back launches)
+    pd.plan = pl;
     pd.launched = true;
     pd.count += 1;
     return TRRE_OK;
@@ -1300,8 +1273,7 @@ int enqueue(trre_prog* p, DeviceState* st, ScanCtx* cx, int family, const uint8_
 // list holds, more than 256 cut lines) — the caller runs the buffer through the general family.
 int repair_bytemap_nuls(DeviceState* st, ScanCtx* cx, const Pending& was, size_t* out_len) {
     using namespace trre;
-    static const bool off = getenv("TRRE_NO_NUL_REPAIR") != nullptr;
-    if (off) return -1;
+    if (switches().no_nul_repair) return -1;
     uint32_t count = 0;
     HIP_TRY(hipMemcpyAsync(&count, cx->d_status + 4, 4, hipMemcpyDeviceToHost, was.stream));
     HIP_TRY(hipStreamSynchronize(was.stream));
@@ -1350,6 +1322,263 @@ int repair_bytemap_nuls(DeviceState* st, ScanCtx* cx, const Pending& was, size_t
     return TRRE_OK;
 }
 
+// ---- finish(): what a launch left behind, outcome by outcome.  The scan that is being finished, as the outcomes hand it round:
+struct Finishing { trre_prog* p; DeviceState* st; ScanCtx* cx; const Pending& was; size_t* out_len; };
+constexpr int kGoOn = 1;                      // an outcome has nothing to return yet (positive: no TRRE_E_* code): finish_inner goes on down its list
+int finish_inner(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len);
+
+// the status word and the output size come down; the stream is idle afterwards
+int fetch_status(ScanCtx* cx, const Pending& was, uint32_t* status) {
+    HIP_TRY(hipMemcpyAsync(cx->h_status, cx->d_status, 8, hipMemcpyDeviceToHost, was.stream));
+    if (was.total_at) HIP_TRY(hipMemcpyAsync(cx->h_status + 2, was.total_at, 8, hipMemcpyDeviceToHost, was.stream));
+    HIP_TRY(hipStreamSynchronize(was.stream));
+    *status = cx->h_status[0];
+    return TRRE_OK;
+}
+
+// The same scan again — as `family`, over the first n bytes — with one route switched off (`off`, a flag of the context; null: none): counted
+// as a relaunch, enqueued, finished, the flag restored on every path.  hold false: the flag covers the enqueue alone, and whatever the
+// finish has to run again sees it cleared (the exact sub-ranges: a rerun of the rerun tries them afresh).
+int rerun(const Finishing& f, int family, bool ScanCtx::*off = nullptr, bool hold = true, size_t n = ~(size_t)0) {
+    ScanCtx* cx = f.cx;
+    if (off) cx->*off = true;
+    cx->relaunches += 1;
+    int rc = enqueue(f.p, f.st, cx, family, f.was.d_in, n == ~(size_t)0 ? f.was.n : n, f.was.d_out, f.was.cap, f.was.stream);
+    if (off && !hold) cx->*off = false;
+    if (!rc) rc = finish_inner(f.p, f.st, cx, f.out_len);
+    if (off) cx->*off = false;
+    return rc;
+}
+
+// Rounds of the lazy family (lazy_block.hpp): the edges the launch listed are built on the host (trre_dft.c:1135-1175: nft_step, truncate_lcp,
+// the lookup, the finality probe), the new rows go up, the lanes that were void walk again.  Every round explores at least one edge
+// of a finite table over a finite input, so this ends — with the answer, or with the memory limit of the tables.
+int lazy_rounds(const Finishing& f, uint32_t* status_io) {
+    using namespace trre;
+    trre_prog* p = f.p; ScanCtx* cx = f.cx; const Pending& was = f.was; size_t* out_len = f.out_len;
+    uint32_t status = *status_io;
+    ScanArgs args = base_args(was.d_in, was.n, was.d_out);
+    args.status = cx->d_status;
+    args.cap = was.cap;
+    args.lane_counts = cx->d_lane_counts;
+    args.chunk_total = cx->d_chunk_total;
+    args.chunk_base = cx->d_chunk_base;
+    std::vector<uint32_t> miss;
+    size_t spec = 1024;
+    int empty_rounds = 0;
+    for (int round = 1; (status & kStMiss) && !(status & (kStEditOverflow | kStDiverge)); ++round) {
+        uint32_t head[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(head, cx->d_miss, 8, hipMemcpyDeviceToHost, was.stream));
+        HIP_TRY(hipStreamSynchronize(was.stream));
+        const uint32_t n_miss = head[0] < kLazyMissCap ? head[0] : kLazyMissCap;
+        // a void lane lists the edge it stopped at unless this very launch has listed it (or the list was full: then it holds other
+        // edges), so a round with a miss and an empty list cannot be — if it is, the device's rows go up afresh, and the scan gives up
+        // rather than spin
+        if (!n_miss) {
+            if (++empty_rounds > 3) return fail_empty(out_len, TRRE_E_DEVICE, "error: the lazy tables make no progress (a miss with nothing listed, four rounds running)");
+            std::lock_guard<std::mutex> lock(p->lazy_mu);
+            f.st->lazy_rows_up = 0;
+        } else {
+            empty_rounds = 0;
+        }
+        miss.resize((size_t)trre::kLazyMissWords * n_miss + 2);
+        if (n_miss) HIP_TRY(hipMemcpyAsync(miss.data(), cx->d_miss + 2, (size_t)n_miss * trre::kLazyMissWords * 4, hipMemcpyDeviceToHost, was.stream));
+        HIP_TRY(hipStreamSynchronize(was.stream));
+        try {
+            std::lock_guard<std::mutex> lock(p->lazy_mu);
+            p->lazy->explore(miss.data(), n_miss, spec);
+        } catch (const trre::Error& e) {
+            return fail_empty(out_len, e.code, e.what());
+        } catch (const std::bad_alloc&) {
+            return fail_empty(out_len, TRRE_E_TOO_BIG, "error: out of memory while determinising");
+        }
+        if (switches().trace) fprintf(stderr, "trre: lazy round %d: %u misses, %u rows, %u states\n", round, n_miss, p->lazy->n_rows(), p->lazy->n_states());
+        // the automatic choice for a pattern that also has its eager tables: a scan that is still growing the lazy ones after kLazyAutoRounds
+        // goes to the tile kernels (the next scan finds the tables that much further)
+        constexpr int kLazyAutoRounds = 64;
+        if (round >= kLazyAutoRounds && !p->forced_family && !p->lazy_only && p->has_engine_tables) return rerun(f, TRRE_KERNEL_TILE_GEN);
+        if (spec < (1u << 16)) spec *= 2;                      // (the deeper the input digs, the further ahead the host looks)
+        HIP_TRY(hipMemsetAsync(cx->d_status, 0, 8, was.stream));
+        cx->relaunches += 1;
+        int rc = lazy_round(p, f.st, cx, args, was.plan.n_chunks, false, was.stream);
+        if (!rc) rc = fetch_status(cx, was, &status);
+        if (rc) return rc;
+    }
+    *status_io = status;
+    // (an edge whose closure runs round an epsilon cycle: the reference dies there with its output unflushed)
+    if (status & kStDiverge) return fail_empty(out_len, TRRE_E_DIVERGES, kDivergeMsg);
+    if (status & kStEditOverflow)
+        return fail_empty(out_len, TRRE_E_UNSUPPORTED, "error: a sub-range of 1 KiB takes more than 2^32 table steps (TRRE_LAZY_BUDGET): lines of megabytes with an attempt per byte");
+    return kGoOn;
+}
+
+// exact sub-ranges, every entry state verified: the sizes are final — the exclusive sum and the emit pass again, counted as a relaunch
+int exact_emit_again(const Finishing& f, trre::ScanArgs& xa) {
+    const LaunchPlan& pl = f.was.plan;
+    trre::launch_chunk_scan(f.cx->d_chunk_total, f.cx->d_chunk_base, pl.n_chunks, f.was.stream);
+    xa.exact = 2;
+    trre::launch_direct_kernel(2, pl.direct_ent_lds, xa, pl.lane_bytes, pl.n_chunks, f.was.stream, pl.g16, pl.sym_mode, pl.g16_slow);
+    HIP_TRY(hipGetLastError());
+    f.cx->relaunches += 1;
+    return TRRE_OK;
+}
+
+// exact sub-ranges, the backward pass guessed wrong somewhere: its flagged lanes sweep again (and on to the left while what they arrive with is
+// not what was assumed there) until every guess is what the lane to the right found; then the forward passes run — they had left at once
+int exact_repair_backward(const Finishing& f, uint32_t rev_misses, uint32_t* misses, uint32_t* status) {
+    using namespace trre;
+    ScanCtx* cx = f.cx; const Pending& was = f.was; const LaunchPlan& pl = was.plan;
+    ScanArgs xa = pl.args;
+    for (int64_t round = 0; rev_misses; ++round) {
+        if (switches().trace) fprintf(stderr, "trre: exact sub-ranges, backward pass: round %lld, %u lane(s) to repair\n", (long long)round, rev_misses);
+        HIP_TRY(hipMemsetAsync(cx->d_status + 2, 0, 4, was.stream));
+        launch_rev_repair(xa, pl.rev_lane_bytes, was.stream, pl.sym_mode == 2);
+        launch_rev_verify(xa, pl.rev_lane_bytes, was.stream, pl.sym_mode == 2);
+        HIP_TRY(hipMemcpyAsync(&rev_misses, cx->d_status + 2, 4, hipMemcpyDeviceToHost, was.stream));
+        HIP_TRY(hipStreamSynchronize(was.stream));
+    }
+    HIP_TRY(hipMemsetAsync(cx->d_status, 0, 16, was.stream));
+    xa.exact = 1;
+    launch_direct_kernel(1, pl.direct_ent_lds, xa, pl.lane_bytes, pl.n_chunks, was.stream, pl.g16, pl.sym_mode, pl.g16_slow);
+    launch_spec_verify(xa, (xa.vend + pl.lane_bytes - 1) / pl.lane_bytes, was.stream);
+    const int rc = exact_emit_again(f, xa);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(misses, cx->d_status + 3, 4, hipMemcpyDeviceToHost, was.stream));
+    return fetch_status(cx, was, status);
+}
+
+// exact sub-ranges: lanes whose guessed entry state was not the exit state of the lane before them walk again (and on, while
+// their exit keeps differing from what the next lane assumed), until k_spec_verify finds none; then the sizes are final
+int exact_repair(const Finishing& f, uint32_t* status) {
+    using namespace trre;
+    ScanCtx* cx = f.cx; const Pending& was = f.was; const LaunchPlan& pl = was.plan;
+    uint32_t both[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(both, cx->d_status + 2, 8, hipMemcpyDeviceToHost, was.stream));
+    HIP_TRY(hipStreamSynchronize(was.stream));
+    uint32_t misses = both[1];
+    if (both[0] && is_guided(was.family)) {
+        const int rc = exact_repair_backward(f, both[0], &misses, status);
+        if (rc) return rc;
+    }
+    if (!misses || (*status & (kStOverflow | kStDiverge))) return kGoOn;
+    ScanArgs xa = pl.args;
+    const int64_t n_lanes = (xa.vend + pl.lane_bytes - 1) / pl.lane_bytes;
+    for (int64_t round = 0; misses; ++round) {
+        if (switches().trace) fprintf(stderr, "trre: exact sub-ranges: round %lld, %u lane(s) to repair\n", (long long)round, misses);
+        if (round > pl.n_chunks + 64)           // (every round settles at least the first flagged lane's workgroup: cannot happen)
+            return rerun(f, was.family, &ScanCtx::exact_off, false);
+        HIP_TRY(hipMemsetAsync(cx->d_status + 3, 0, 4, was.stream));
+        xa.exact = 3;
+        launch_direct_kernel(1, pl.direct_ent_lds, xa, pl.lane_bytes, pl.n_chunks, was.stream, pl.g16, pl.sym_mode, pl.g16_slow);
+        launch_spec_verify(xa, n_lanes, was.stream);
+        HIP_TRY(hipMemcpyAsync(&misses, cx->d_status + 3, 4, hipMemcpyDeviceToHost, was.stream));
+        HIP_TRY(hipStreamSynchronize(was.stream));
+    }
+    int rc = exact_emit_again(f, xa);
+    if (!rc) rc = fetch_status(cx, was, status);
+    return rc ? rc : kGoOn;
+}
+
+// the one-pass kernels' phase clocks (TRRE_ONE_PROF, TRRE_MAPGEN_PROF) on stderr, the memoryless kernel's tiles (TRRE_MAPGEN_DBG) to their file
+int profile_dumps(ScanCtx* cx, const Pending& was) {
+    const trre::Switches& sw = trre::switches();
+    uint64_t pr[8] = {};
+    if ((was.one && sw.one_prof) || (was.mapgen && sw.mapgen_prof)) HIP_TRY(hipMemcpy(pr, was.total_at + 1, sizeof(pr), hipMemcpyDeviceToHost));
+    const double t = pr[7] ? (double)pr[7] : 1.0;
+    if (was.one && sw.one_prof)
+        fprintf(stderr, "trre: one-pass phases, shader clocks per tile (%llu tiles): ticket %.0f  walk %.0f  verify %.0f  sizes %.0f  look-back %.0f  store %.0f\n",
+                (unsigned long long)pr[7], pr[0] / t, pr[1] / t, pr[2] / t, pr[3] / t, pr[4] / t, pr[5] / t);
+    if (was.mapgen && sw.mapgen_prof)
+        fprintf(stderr, "trre: memoryless kernel, shader clocks per trip (%llu trips): look-back %.0f  expand %.0f  next tile counted %.0f  store %.0f  barrier %.0f\n",
+                (unsigned long long)pr[7], pr[1] / t, pr[2] / t, pr[3] / t, pr[4] / t, pr[5] / t);
+    if (was.mapgen && sw.mapgen_dbg) {
+        std::vector<uint64_t> d(16 * cx->d_mg.cap);
+        HIP_TRY(hipMemcpy(d.data(), was.total_at + 1 + 8, d.size() * 8, hipMemcpyDeviceToHost));
+        if (FILE* f = fopen(sw.mapgen_dbg, "wb")) { fwrite(d.data(), 8, d.size(), f); fclose(f); }
+    }
+    return kGoOn;
+}
+
+// A scan that met an attempt which does not return.  The NFT binary exits with everything it had printed so far (exit() flushes stdout):
+// the lines before the bad one and the bad line's output up to the attempt that does not return.  The guided tables stop a lane exactly
+// there (guided_build.cpp), the count pass names the first such lane in stream order and knows every lane's size: the output up to that
+// point is in the buffer and its length is reported with the error.  (The DFT binary dies of unbounded recursion, its buffered output is
+// lost: nothing to reproduce, *out_len = 0.)
+int report_divergence(const Finishing& f) {
+    trre_prog* p = f.p; ScanCtx* cx = f.cx; const Pending& was = f.was; size_t* out_len = f.out_len;
+    if (out_len) *out_len = 0;
+    const bool knows_lane = (was.family == TRRE_KERNEL_GUIDED_GEN && !was.patched) || was.family == TRRE_KERNEL_BACKTRACK;
+    if (p->engine != TRRE_ENGINE_NFT || (!p->gt.ok && !p->bt_ok)) return fail(TRRE_E_DIVERGES, kDivergeMsg);
+    if (!knows_lane) {
+        // (the count / emit pair knows every lane's size; the rerun comes back here through the branch below)
+        const int rc = rerun(f, p->gt.ok ? TRRE_KERNEL_GUIDED_GEN : TRRE_KERNEL_BACKTRACK, &ScanCtx::patch_off);
+        return rc == TRRE_OK ? fail(TRRE_E_DEVICE, "error: a diverging scan did not diverge when it was run again") : rc;
+    }
+    const uint32_t lane = 0xffffffffu - cx->h_status[1];
+    const int64_t chunk = (int64_t)lane / 256;             // (workspace chunks are 256 lanes: ensure_workspace)
+    std::vector<uint32_t> counts(256);
+    uint64_t base = 0, chunk_total = 0;
+    HIP_TRY(hipMemcpyAsync(counts.data(), cx->d_lane_counts + chunk * 256, 256 * 4, hipMemcpyDeviceToHost, was.stream));
+    HIP_TRY(hipMemcpyAsync(&base, cx->d_chunk_base + chunk, 8, hipMemcpyDeviceToHost, was.stream));
+    HIP_TRY(hipMemcpyAsync(&chunk_total, cx->d_chunk_total + chunk, 8, hipMemcpyDeviceToHost, was.stream));
+    HIP_TRY(hipStreamSynchronize(was.stream));
+    uint64_t upto = base;
+    for (uint32_t k = 0; k <= lane % 256; ++k) upto += counts[k];
+    if (base + chunk_total > was.cap) {                    // the emit pass skipped this chunk: ask for room, the retry reports
+        if (out_len) *out_len = (size_t)(base + chunk_total);
+        return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    }
+    if (out_len) *out_len = (size_t)upto;
+    return fail(TRRE_E_DIVERGES, kDivergeMsg);
+}
+
+// The backtracking fallback ran into a limit.  Which one: an attempt deeper than a lane's stack or with more output than its path buffer
+// runs again with fewer, larger ones; the step budget is final (the reference's search is exponential here too)
+int backtrack_retry(const Finishing& f) {
+    ScanCtx* cx = f.cx;
+    uint32_t why = 0;
+    HIP_TRY(hipMemcpyAsync(&why, cx->d_status + 2, 4, hipMemcpyDeviceToHost, f.was.stream));
+    HIP_TRY(hipStreamSynchronize(f.was.stream));
+    if (!(why & trre::kBtWhyBudget) && cx->bt_tier < kBtTierCount - 1) {
+        const int tier = cx->bt_tier;
+        cx->bt_tier = tier + 1;
+        const int rc = rerun(f, f.was.family);
+        cx->bt_tier = tier;
+        return rc;
+    }
+    return fail_empty(f.out_len, TRRE_E_UNSUPPORTED, (why & trre::kBtWhyBudget) ? "error: the search takes more than 16 M steps in 1 KiB of this input (TRRE_BT_BUDGET; the backtracking fallback)"
+                                                                : "error: an attempt of the search consumes more than 1 M bytes or prints more than 1 MiB (the backtracking fallback)");
+}
+
+// One-pass launches that were void, and what a good one of the memoryless kernel says about the corpus.
+int one_pass_outcome(const Finishing& f, uint32_t status) {
+    using namespace trre;
+    ScanCtx* cx = f.cx; const Pending& was = f.was;
+    if (was.mapgen && (status & (kStNul | kStOneVoid))) {
+        // a NUL cuts its record short — the rest of the record is swallowed: state after all — (or a look-back that gave up: a workgroup of
+        // the grid was not resident — another process on the device —, tests: TRRE_MAPGEN_OVERSUB): the general small-table family takes the buffer
+        if (switches().trace) fprintf(stderr, "trre: a one-pass launch of the memoryless kernel was void: status 0x%x\n", status);
+        cx->mapgen_voids += 1;
+        return rerun(f, was.family, &ScanCtx::mapgen_off);
+    }
+    if (was.mapgen) {
+        // (the longer texts are frequent in what this context scans: see make_plan())
+        uint64_t m = 0;
+        std::memcpy(&m, cx->h_status + 2, 8);
+        if (m > (uint64_t)was.n + (uint64_t)was.n / 25) cx->mapgen_dense = true;
+    }
+    if (was.one && (status & kStOneVoid)) {
+        // the one-pass kernel could not answer (one_block.hpp: what voids it): the count / emit pair takes the buffer — and, the corpus being
+        // what it is, after two such launches the program's later scans too
+        if (switches().trace) fprintf(stderr, "trre: a one-pass launch of family %d was void: status 0x%x\n", was.family, status);
+        f.p->one_fails.fetch_add(1);
+        return rerun(f, was.family, &ScanCtx::one_off);
+    }
+    return kGoOn;
+}
+
+// The outcomes of a launch in the order they are believed — the order matters: a length-preserving launch that met a NUL, say, is void
+// before its divergence bit is looked at.
 int finish_inner(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
     using namespace trre;
     Pending& pd = cx->pend;
@@ -1361,325 +1590,62 @@ int finish_inner(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
         if (out_len) *out_len = was.n;
         return fail(TRRE_E_CAPACITY, "error: output buffer too small");
     }
+    const Finishing f{p, st, cx, was, out_len};
+    uint32_t status = 0;
     if (was.timed) HIP_TRY(hipEventRecord(cx->ev1, was.stream));
-    HIP_TRY(hipMemcpyAsync(cx->h_status, cx->d_status, 8, hipMemcpyDeviceToHost, was.stream));
-    if (was.total_at) HIP_TRY(hipMemcpyAsync(cx->h_status + 2, was.total_at, 8, hipMemcpyDeviceToHost, was.stream));
-    HIP_TRY(hipStreamSynchronize(was.stream));
+    int rc = fetch_status(cx, was, &status);
+    if (rc) return rc;
     if (was.timed) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, cx->ev0, cx->ev1));
         p->last_ms = ms / (float)(was.count > 0 ? was.count : 1);   // average per launch of the batch
     }
-    uint32_t status = cx->h_status[0];
-    if (was.family == TRRE_KERNEL_DFT_LAZY) {
-        // Rounds (lazy_block.hpp): the edges the launch listed are built on the host (trre_dft.c:1135-1175: nft_step, truncate_lcp, the
-        // lookup, the finality probe), the new rows go up, the lanes that were void walk again.  Every round explores at least one edge
-        // of a finite table over a finite input, so this ends — with the answer, or with the memory limit of the tables.
-        const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(was.d_in) & 15u);
-        ScanArgs args{};
-        args.in_v0 = was.d_in - a0;
-        args.out_v0 = was.d_out - a0;
-        args.out = was.d_out;
-        args.vbeg = a0;
-        args.vend = a0 + (int64_t)was.n;
-        args.status = cx->d_status;
-        args.cap = was.cap;
-        args.lane_counts = cx->d_lane_counts;
-        args.chunk_total = cx->d_chunk_total;
-        args.chunk_base = cx->d_chunk_base;
-        const int64_t n_chunks = (args.vend + kLazyLaneBytes * 256 - 1) / (kLazyLaneBytes * 256);
-        std::vector<uint32_t> miss;
-        size_t spec = 1024;
-        int empty_rounds = 0;
-        static const bool lazy_trace = getenv("TRRE_TRACE") != nullptr;
-        for (int round = 1; (status & kStMiss) && !(status & (kStEditOverflow | kStDiverge)); ++round) {
-            uint32_t head[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(head, cx->d_miss, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipStreamSynchronize(was.stream));
-            const uint32_t n_miss = head[0] < kLazyMissCap ? head[0] : kLazyMissCap;
-            // a void lane lists the edge it stopped at unless this very launch has listed it (or the list was full: then it holds other
-            // edges), so a round with a miss and an empty list cannot be — if it is, the device's rows go up afresh, and the scan gives up
-            // rather than spin
-            if (!n_miss) {
-                if (++empty_rounds > 3) {
-                    if (out_len) *out_len = 0;
-                    return fail(TRRE_E_DEVICE, "error: the lazy tables make no progress (a miss with nothing listed, four rounds running)");
-                }
-                std::lock_guard<std::mutex> lock(p->lazy_mu);
-                st->lazy_rows_up = 0;
-            } else {
-                empty_rounds = 0;
-            }
-            miss.resize((size_t)trre::kLazyMissWords * n_miss + 2);
-            if (n_miss) HIP_TRY(hipMemcpyAsync(miss.data(), cx->d_miss + 2, (size_t)n_miss * trre::kLazyMissWords * 4, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipStreamSynchronize(was.stream));
-            try {
-                std::lock_guard<std::mutex> lock(p->lazy_mu);
-                p->lazy->explore(miss.data(), n_miss, spec);
-            } catch (const trre::Error& e) {
-                if (out_len) *out_len = 0;
-                return fail(e.code, e.what());
-            } catch (const std::bad_alloc&) {
-                if (out_len) *out_len = 0;
-                return fail(TRRE_E_TOO_BIG, "error: out of memory while determinising");
-            }
-            if (lazy_trace) fprintf(stderr, "trre: lazy round %d: %u misses, %u rows, %u states\n", round, n_miss, p->lazy->n_rows(), p->lazy->n_states());
-            // the automatic choice for a pattern that also has its eager tables: a scan that is still growing the lazy ones after kLazyAutoRounds
-            // goes to the tile kernels (the next scan finds the tables that much further)
-            constexpr int kLazyAutoRounds = 64;
-            if (round >= kLazyAutoRounds && !p->forced_family && !p->lazy_only && p->has_engine_tables) {
-                cx->relaunches += 1;
-                const int rc = enqueue(p, st, cx, TRRE_KERNEL_TILE_GEN, was.d_in, was.n, was.d_out, was.cap, was.stream);
-                return rc ? rc : finish_inner(p, st, cx, out_len);
-            }
-            if (spec < (1u << 16)) spec *= 2;                      // (the deeper the input digs, the further ahead the host looks)
-            HIP_TRY(hipMemsetAsync(cx->d_status, 0, 8, was.stream));
-            cx->relaunches += 1;
-            const int rc = lazy_round(p, st, cx, args, n_chunks, false, was.stream);
-            if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(cx->h_status, cx->d_status, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipMemcpyAsync(cx->h_status + 2, was.total_at, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipStreamSynchronize(was.stream));
-            status = cx->h_status[0];
-        }
-        if (status & kStDiverge) {      // an edge whose closure runs round an epsilon cycle: the reference dies there with its output unflushed
-            if (out_len) *out_len = 0;
-            return fail(TRRE_E_DIVERGES, "error: stack max capacity reached (the reference's search does not terminate on this input)");
-        }
-        if (status & kStEditOverflow) {
-            if (out_len) *out_len = 0;
-            return fail(TRRE_E_UNSUPPORTED, "error: a sub-range of 1 KiB takes more than 2^32 table steps (TRRE_LAZY_BUDGET): lines of megabytes with an attempt per byte");
-        }
-    }
-    if (was.exact && !(status & (kStOverflow | kStDiverge))) {
-        // exact sub-ranges: lanes whose guessed entry state was not the exit state of the lane before them walk again (and on, while
-        // their exit keeps differing from what the next lane assumed), until k_spec_verify finds none; then the sizes are final
-        uint32_t both[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(both, cx->d_status + 2, 8, hipMemcpyDeviceToHost, was.stream));
-        HIP_TRY(hipStreamSynchronize(was.stream));
-        uint32_t misses = both[1];
-        static const bool spec_trace0 = getenv("TRRE_TRACE") != nullptr;
-        if (both[0] && was.x_rev_lane_bytes) {
-            // the backward pass guessed wrong somewhere: its flagged lanes sweep again (and on to the left while what they arrive with is not what
-            // was assumed there) until every guess is what the lane to the right found; then the forward passes run — they had left at once
-            ScanArgs xa = was.xargs;
-            uint32_t rev_misses = both[0];
-            for (int64_t round = 0; rev_misses; ++round) {
-                if (spec_trace0) fprintf(stderr, "trre: exact sub-ranges, backward pass: round %lld, %u lane(s) to repair\n", (long long)round, rev_misses);
-                HIP_TRY(hipMemsetAsync(cx->d_status + 2, 0, 4, was.stream));
-                launch_rev_repair(xa, was.x_rev_lane_bytes, was.stream, was.x_sym == 2);
-                launch_rev_verify(xa, was.x_rev_lane_bytes, was.stream, was.x_sym == 2);
-                HIP_TRY(hipMemcpyAsync(&rev_misses, cx->d_status + 2, 4, hipMemcpyDeviceToHost, was.stream));
-                HIP_TRY(hipStreamSynchronize(was.stream));
-            }
-            HIP_TRY(hipMemsetAsync(cx->d_status, 0, 16, was.stream));
-            xa.exact = 1;
-            launch_direct_kernel(1, was.x_ent_lds, xa, was.x_lane_bytes, was.x_n_chunks, was.stream, was.x_g16, was.x_sym, was.x_slow);
-            launch_spec_verify(xa, (xa.vend + was.x_lane_bytes - 1) / was.x_lane_bytes, was.stream);
-            launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, was.x_n_chunks, was.stream);
-            xa.exact = 2;
-            launch_direct_kernel(2, was.x_ent_lds, xa, was.x_lane_bytes, was.x_n_chunks, was.stream, was.x_g16, was.x_sym, was.x_slow);
-            HIP_TRY(hipGetLastError());
-            cx->relaunches += 1;
-            HIP_TRY(hipMemcpyAsync(cx->h_status, cx->d_status, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipMemcpyAsync(cx->h_status + 2, was.total_at, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipMemcpyAsync(&misses, cx->d_status + 3, 4, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipStreamSynchronize(was.stream));
-            status = cx->h_status[0];
-        }
-        if (misses && !(status & (kStOverflow | kStDiverge))) {
-            ScanArgs xa = was.xargs;
-            const int64_t n_lanes = (xa.vend + was.x_lane_bytes - 1) / was.x_lane_bytes;
-            static const bool spec_trace = getenv("TRRE_TRACE") != nullptr;
-            for (int64_t round = 0; misses; ++round) {
-                if (spec_trace) fprintf(stderr, "trre: exact sub-ranges: round %lld, %u lane(s) to repair\n", (long long)round, misses);
-                if (round > was.x_n_chunks + 64) {           // (every round settles at least the first flagged lane's workgroup: cannot happen)
-                    cx->exact_off = true;
-                    const int rc = enqueue(p, st, cx, was.family, was.d_in, was.n, was.d_out, was.cap, was.stream);
-                    cx->exact_off = false;
-                    cx->relaunches += 1;
-                    return rc ? rc : finish_inner(p, st, cx, out_len);
-                }
-                HIP_TRY(hipMemsetAsync(cx->d_status + 3, 0, 4, was.stream));
-                xa.exact = 3;
-                launch_direct_kernel(1, was.x_ent_lds, xa, was.x_lane_bytes, was.x_n_chunks, was.stream, was.x_g16, was.x_sym, was.x_slow);
-                launch_spec_verify(xa, n_lanes, was.stream);
-                HIP_TRY(hipMemcpyAsync(&misses, cx->d_status + 3, 4, hipMemcpyDeviceToHost, was.stream));
-                HIP_TRY(hipStreamSynchronize(was.stream));
-            }
-            launch_chunk_scan(cx->d_chunk_total, cx->d_chunk_base, was.x_n_chunks, was.stream);
-            xa.exact = 2;
-            launch_direct_kernel(2, was.x_ent_lds, xa, was.x_lane_bytes, was.x_n_chunks, was.stream, was.x_g16, was.x_sym, was.x_slow);
-            HIP_TRY(hipGetLastError());
-            cx->relaunches += 1;
-            HIP_TRY(hipMemcpyAsync(cx->h_status, cx->d_status, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipMemcpyAsync(cx->h_status + 2, was.total_at, 8, hipMemcpyDeviceToHost, was.stream));
-            HIP_TRY(hipStreamSynchronize(was.stream));
-            status = cx->h_status[0];
-        }
-    }
-    if (was.one && getenv("TRRE_ONE_PROF")) {
-        uint64_t pr[8] = {};
-        HIP_TRY(hipMemcpy(pr, was.total_at + 1, sizeof(pr), hipMemcpyDeviceToHost));
-        const double t = pr[7] ? (double)pr[7] : 1.0;
-        fprintf(stderr, "trre: one-pass phases, shader clocks per tile (%llu tiles): ticket %.0f  walk %.0f  verify %.0f  sizes %.0f  look-back %.0f  store %.0f\n",
-                (unsigned long long)pr[7], pr[0] / t, pr[1] / t, pr[2] / t, pr[3] / t, pr[4] / t, pr[5] / t);
-    }
-    if (was.mapgen && getenv("TRRE_MAPGEN_PROF")) {
-        uint64_t pr[8] = {};
-        HIP_TRY(hipMemcpy(pr, was.total_at + 1, sizeof(pr), hipMemcpyDeviceToHost));
-        const double t = pr[7] ? (double)pr[7] : 1.0;
-        fprintf(stderr, "trre: memoryless kernel, shader clocks per trip (%llu trips): look-back %.0f  expand %.0f  next tile counted %.0f  store %.0f  barrier %.0f\n",
-                (unsigned long long)pr[7], pr[1] / t, pr[2] / t, pr[3] / t, pr[4] / t, pr[5] / t);
-    }
-    if (was.mapgen && getenv("TRRE_MAPGEN_DBG")) {
-        const int64_t nt = ((int64_t)was.n + 15 + kMapGenTile) / kMapGenTile + 1;
-        std::vector<uint64_t> d(16 * (size_t)cx->mg_tiles);
-        HIP_TRY(hipMemcpy(d.data(), was.total_at + 1 + 8, d.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(getenv("TRRE_MAPGEN_DBG"), "wb")) { fwrite(d.data(), 8, d.size(), f); fclose(f); }
-        (void)nt;
-    }
-    if (was.mapgen && (status & (kStNul | kStOneVoid))) {
-        // a NUL cuts its record short — the rest of the record is swallowed: state after all — (or a look-back that gave up: a workgroup of
-        // the grid was not resident — another process on the device —, tests: TRRE_MAPGEN_OVERSUB): the general small-table family takes the buffer
-        static const bool mg_trace = getenv("TRRE_TRACE") != nullptr;
-        if (mg_trace) fprintf(stderr, "trre: a one-pass launch of the memoryless kernel was void: status 0x%x\n", status);
-        cx->mapgen_off = true;
-        cx->mapgen_voids += 1;
-        cx->relaunches += 1;
-        int rc = enqueue(p, st, cx, was.family, was.d_in, was.n, was.d_out, was.cap, was.stream);
-        if (!rc) rc = finish_inner(p, st, cx, out_len);
-        cx->mapgen_off = false;
-        return rc;
-    }
-    if (was.mapgen) {
-        // (the longer texts are frequent in what this context scans: see enqueue())
-        uint64_t m = 0;
-        std::memcpy(&m, cx->h_status + 2, 8);
-        if (m > (uint64_t)was.n + (uint64_t)was.n / 25) cx->mapgen_dense = true;
-    }
-    if (was.one && (status & kStOneVoid)) {
-        // the one-pass kernel could not answer (one_block.hpp: what voids it): the count / emit pair takes the buffer — and, the corpus being
-        // what it is, after two such launches the program's later scans too
-        static const bool one_trace = getenv("TRRE_TRACE") != nullptr;
-        if (one_trace) fprintf(stderr, "trre: a one-pass launch of family %d was void: status 0x%x\n", was.family, status);
-        p->one_fails.fetch_add(1);
-        cx->one_off = true;
-        cx->relaunches += 1;
-        int rc = enqueue(p, st, cx, was.family, was.d_in, was.n, was.d_out, was.cap, was.stream);
-        if (!rc) rc = finish_inner(p, st, cx, out_len);
-        cx->one_off = false;
-        return rc;
-    }
-    if ((was.exact || was.one) && (status & kStDiverge)) {
-        // an attempt that does not return: the lane bookkeeping of the error path (the first such lane in stream order, the sizes of the lanes
-        // before it) is that of lanes that own lines — the same scan again, the old way
-        cx->exact_off = true;
-        const int rc = enqueue(p, st, cx, was.family, was.d_in, was.n, was.d_out, was.cap, was.stream);
-        cx->exact_off = false;
-        cx->relaunches += 1;
-        return rc ? rc : finish_inner(p, st, cx, out_len);
-    }
-    auto again = [&](int family) -> int {
-        cx->relaunches += 1;
-        int rc = enqueue(p, st, cx, family, was.d_in, was.n, was.d_out, was.cap, was.stream);
-        if (rc) return rc;
-        return finish_inner(p, st, cx, out_len);
-    };
+    rc = was.family == TRRE_KERNEL_DFT_LAZY ? lazy_rounds(f, &status) : kGoOn;
+    if (rc == kGoOn && was.exact && !(status & (kStOverflow | kStDiverge))) rc = exact_repair(f, &status);
+    if (rc == kGoOn) rc = profile_dumps(cx, was);
+    if (rc == kGoOn) rc = one_pass_outcome(f, status);
+    if (rc != kGoOn) return rc;
+    // an attempt that does not return: the lane bookkeeping of the error path (the first such lane in stream order, the sizes of the lanes
+    // before it) is that of lanes that own lines — the same scan again, the old way
+    if ((was.exact || was.one) && (status & kStDiverge)) return rerun(f, was.family, &ScanCtx::exact_off, false);
     // (a length-preserving launch that met a NUL is void — it went on walking behind the NUL, where the reference never
     // looks — and so is whatever else it reports: the general family decides, below)
     const bool void_by_nul = !is_gen(was.family) && (status & kStNul);
-    if ((status & kStDiverge) && !void_by_nul) {
-        const char* msg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
-        if (out_len) *out_len = 0;
-        // The NFT binary exits with everything it had printed so far (exit() flushes stdout): the lines before the bad one
-        // and the bad line's output up to the attempt that does not return.  The guided tables stop a lane exactly there
-        // (guided_build.cpp), the count pass names the first such lane in stream order and knows every lane's size: the
-        // output up to that point is in the buffer and its length is reported with the error.  (The DFT binary dies of
-        // unbounded recursion, its buffered output is lost: nothing to reproduce, *out_len = 0.)
-        const bool knows_lane = (was.family == TRRE_KERNEL_GUIDED_GEN && !was.patched) || was.family == TRRE_KERNEL_BACKTRACK;
-        if (p->engine != TRRE_ENGINE_NFT || (!p->gt.ok && !p->bt_ok)) return fail(TRRE_E_DIVERGES, msg);
-        if (!knows_lane) {
-            cx->patch_off = true;                              // (the count / emit pair knows every lane's size)
-            const int rc = again(p->gt.ok ? TRRE_KERNEL_GUIDED_GEN : TRRE_KERNEL_BACKTRACK);      // (comes back here through the branch below)
-            cx->patch_off = false;
-            return rc == TRRE_OK ? fail(TRRE_E_DEVICE, "error: a diverging scan did not diverge when it was run again") : rc;
-        }
-        const uint32_t lane = 0xffffffffu - cx->h_status[1];
-        const int64_t chunk = (int64_t)lane / 256;             // (workspace chunks are 256 lanes: ensure_workspace)
-        std::vector<uint32_t> counts(256);
-        uint64_t base = 0, chunk_total = 0;
-        HIP_TRY(hipMemcpyAsync(counts.data(), cx->d_lane_counts + chunk * 256, 256 * 4, hipMemcpyDeviceToHost, was.stream));
-        HIP_TRY(hipMemcpyAsync(&base, cx->d_chunk_base + chunk, 8, hipMemcpyDeviceToHost, was.stream));
-        HIP_TRY(hipMemcpyAsync(&chunk_total, cx->d_chunk_total + chunk, 8, hipMemcpyDeviceToHost, was.stream));
-        HIP_TRY(hipStreamSynchronize(was.stream));
-        uint64_t upto = base;
-        for (uint32_t k = 0; k <= lane % 256; ++k) upto += counts[k];
-        if (base + chunk_total > was.cap) {                    // the emit pass skipped this chunk: ask for room, the retry reports
-            if (out_len) *out_len = (size_t)(base + chunk_total);
-            return fail(TRRE_E_CAPACITY, "error: output buffer too small");
-        }
-        if (out_len) *out_len = (size_t)upto;
-        return fail(TRRE_E_DIVERGES, msg);
-    }
-    if (was.family == TRRE_KERNEL_BACKTRACK && (status & kStEditOverflow)) {
-        // which limit: an attempt deeper than a lane's stack or with more output than its path buffer runs again with fewer, larger ones;
-        // the step budget is final (the reference's search is exponential here too)
-        uint32_t why = 0;
-        HIP_TRY(hipMemcpyAsync(&why, cx->d_status + 2, 4, hipMemcpyDeviceToHost, was.stream));
-        HIP_TRY(hipStreamSynchronize(was.stream));
-        if (!(why & kBtWhyBudget) && cx->bt_tier < kBtTierCount - 1) {
-            const int tier = cx->bt_tier;
-            cx->bt_tier = tier + 1;
-            const int rc = again(was.family);
-            cx->bt_tier = tier;
-            return rc;
-        }
-        if (out_len) *out_len = 0;
-        return fail(TRRE_E_UNSUPPORTED, (why & kBtWhyBudget) ? "error: the search takes more than 16 M steps in 1 KiB of this input (TRRE_BT_BUDGET; the backtracking fallback)"
-                                                              : "error: an attempt of the search consumes more than 1 M bytes or prints more than 1 MiB (the backtracking fallback)");
-    }
+    if ((status & kStDiverge) && !void_by_nul) return report_divergence(f);
+    if (was.family == TRRE_KERNEL_BACKTRACK && (status & kStEditOverflow)) return backtrack_retry(f);
     if (status & kStNeedScratch) {
         // a line longer than the LDS tile met the non-deterministic engine: give it
         // a mask scratch (one mask per input byte) and run again
         const size_t need = (was.n + 32) * (size_t)p->mask_bytes;
-        if (cx->scratch_bytes < need) {
-            if (cx->d_scratch) (void)hipFree(cx->d_scratch);
-            cx->d_scratch = nullptr; cx->scratch_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_scratch), need));
-            cx->scratch_bytes = need;
-        }
-        return again(was.family);
+        HIP_TRY(cx->d_scratch.reserve(need, need));
+        return rerun(f, was.family);
     }
-    static const bool trace_void = getenv("TRRE_TRACE") != nullptr;      // (why a launch was void, on stderr)
-    if (trace_void && was.patched && (status & (kStEditOverflow | kStNul | kStOverflow | kStDiverge)))
+    // (why a launch was void, on stderr)
+    if (switches().trace && was.patched && (status & (kStEditOverflow | kStNul | kStOverflow | kStDiverge)))
         fprintf(stderr, "trre: a mark + splice launch of family %d was void: status 0x%x\n", was.family, status);
     if (was.patched && (status & (kStEditOverflow | kStNul))) {
         // copy
         // form of a large table: more texts in a sub-range (or in 64 bytes of it) than its event list holds, or a NUL byte —
         // the count / emit pair
         if (status & kStEditOverflow) p->copy_form_off.store(true);      // (a property of the dictionary and its corpus: do not try again)
-        cx->patch_off = true;
-        const int rc = again(was.family);
-        cx->patch_off = false;
-        return rc;
+        return rerun(f, was.family, &ScanCtx::patch_off);
     }
     // an undecided attempt outgrew the stream table (bounded fold): the guided (or the tile) kernels take the buffer — this one
     // and, the corpus being what it is, the ones after it (the count pass found out; the emit pass saw the mark and left at once)
     if (is_stream(was.family) && (status & kStOverflow)) {
         p->bounded_off.store(true);
-        return again(general_family(*p, false));
+        return rerun(f, general_family(*p, false));
     }
     if (!is_gen(was.family)) {
         // a NUL cuts its line short, so output positions no longer equal input positions: redo with a general family
         if ((status & kStNul) && was.family == TRRE_KERNEL_BYTEMAP) {
-            const int rc = repair_bytemap_nuls(st, cx, was, out_len);
+            rc = repair_bytemap_nuls(st, cx, was, out_len);
             if (rc >= 0) return rc;
         }
         // (the same repair for the other length-preserving families — the NULs looked up by a pass over the input, the stretches
         // scanned again by the window kernel with unaligned stores — was built and measured in round 4: 13.5 ms for 8 GiB with a
         // NUL per GiB against 12.9 ms for the general family over the whole buffer; not kept.  DESIGN.md §5)
-        if (status & kStNul) return again(general_family(*p, !is_guided(was.family)));
+        if (status & kStNul) return rerun(f, general_family(*p, !is_guided(was.family)));
         if (out_len) *out_len = was.n;
         return TRRE_OK;
     }
@@ -1706,13 +1672,9 @@ int finish_guarded(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) 
     if (grc) return grc;
     if (!hit.hit) return rc;
     size_t pre = 0;
-    if (hit.line_start > 0) {
-        cx->guard_off = true;
-        int rc = enqueue(p, st, cx, was.family, was.d_in, (size_t)hit.line_start, was.d_out, was.cap, was.stream);
-        if (!rc) rc = finish_inner(p, st, cx, &pre);
-        cx->guard_off = false;
-        cx->relaunches += 1;
-        if (rc) { if (out_len) *out_len = pre; return rc; }
+    if (hit.line_start > 0) {                  // the lines before the line the guard stopped at: not to be guarded again
+        const int prc = rerun(Finishing{p, st, cx, was, &pre}, was.family, &ScanCtx::guard_off, true, (size_t)hit.line_start);
+        if (prc) { if (out_len) *out_len = pre; return prc; }
     }
     const size_t part = hit.part == 0xffffffffu ? 0 : hit.part;
     if (out_len) *out_len = pre + part;
@@ -1826,8 +1788,7 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
             make_guard(true);
         } else {
             // TRRE_TRACE=1: the stages of the NFT compile on stderr as they start (to find the one a pattern is slow in)
-            static const bool trace_on = getenv("TRRE_TRACE") != nullptr;
-            auto trace = [&](const char* what) { if (trace_on) fprintf(stderr, "compile: %s\n", what); };
+            auto trace = [&](const char* what) { if (switches().trace) fprintf(stderr, "compile: %s\n", what); };
             trace("nodes");
             const NftNodes nodes = build_nft_nodes(nft);
             p->nft_nodes = (uint32_t)nodes.node.size();
@@ -1843,7 +1804,7 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
                 deferred.reset(new Error(e));            // too many nodes (or an epsilon cycle) for the bitmask kernels
             }
             // the fold walks the follow lists (TRRE_NFT_FOLD=states: the NFT's states as the reference does, =both: both, compared)
-            const char* fold = getenv("TRRE_NFT_FOLD");
+            const char* fold = nft_fold_now();
             trace("fold");
             if (fold && !strcmp(fold, "states")) {
                 p->stt = build_stream_nft(nft);
@@ -1911,12 +1872,7 @@ void trre_free(trre_prog* p) {
     for (auto& kv : p->dev) {
         DeviceState& st = *kv.second;
         (void)hipSetDevice(st.device);
-        (void)hipFree(st.d_blob);
-        (void)hipFree(st.d_sblob);
-        (void)hipFree(st.d_gblob);
-        (void)hipFree(st.d_rblob);
-        (void)hipFree(st.d_nblob);
-        (void)hipFree(st.d_kblob);
+        for (void* b : {(void*)st.d_blob, (void*)st.d_sblob, (void*)st.d_gblob, (void*)st.d_rblob, (void*)st.d_nblob, (void*)st.d_kblob}) (void)hipFree(b);
         (void)hipFree(st.d_lent); (void)hipFree(st.d_lpool); (void)hipFree(st.d_lcls);
         for (void* r : st.retired) (void)hipFree(r);
         ctx_free(st.ctx);
@@ -1974,23 +1930,16 @@ int trre_set_kernel(trre_prog* p, int family) {
     return TRRE_OK;
 }
 
-size_t trre_export_tables(const trre_prog* p, void* buf, size_t cap) {
-    if (!p) return 0;
-    if (buf && cap) std::memcpy(buf, p->blob.data(), cap < p->blob.size() ? cap : p->blob.size());
-    return p->blob.size();
+static size_t export_blob(const std::vector<uint8_t>& b, void* buf, size_t cap) {
+    if (buf && cap) std::memcpy(buf, b.data(), cap < b.size() ? cap : b.size());
+    return b.size();
 }
-
-size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap) {
-    if (!p) return 0;
-    if (buf && cap) std::memcpy(buf, p->sblob.data(), cap < p->sblob.size() ? cap : p->sblob.size());
-    return p->sblob.size();
-}
+size_t trre_export_tables(const trre_prog* p, void* buf, size_t cap) { return p ? export_blob(p->blob, buf, cap) : 0; }
+size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap) { return p ? export_blob(p->sblob, buf, cap) : 0; }
 
 size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap) {
     if (!p) return 0;
-    const std::vector<uint8_t>& b = which == 0 ? p->rblob : (which == 2 ? p->nblob : (which == 3 ? p->kblob : p->gblob));   // (2: the enumeration's / the backtracking fallback's tables, 3: the stack guard's)
-    if (buf && cap) std::memcpy(buf, b.data(), cap < b.size() ? cap : b.size());
-    return b.size();
+    return export_blob(which == 0 ? p->rblob : (which == 2 ? p->nblob : (which == 3 ? p->kblob : p->gblob)), buf, cap);   // (2: the enumeration's / the backtracking fallback's tables, 3: the stack guard's)
 }
 
 // CPU test tier (tests/cpu_shim.cpp runs lazy_block.hpp's lane body on the host): the lazy tables as they stand — which 0: u32 n_cls, u32 rows,
@@ -2112,22 +2061,16 @@ int generate_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, std:
         // The enumeration on the device (gen_block.hpp; TRRE_GEN_HOST=1: on host threads, as in round 3): count, exclusive
         // sum, emit.  A chunk on which a path never returns, a search goes deeper than a lane's stack or the sizes leave 32 bits
         // goes to the host enumeration below, which also knows what the reference had printed when it gave up.
-        static const bool gen_host = getenv("TRRE_GEN_HOST") != nullptr;
         bool done = false;
-        if (!gen_host) {
+        if (!switches().gen_host) {
             const int64_t n_lanes_raw = ((int64_t)len + kGenLaneBytes - 1) / kGenLaneBytes;
             const int64_t n_chunks = (n_lanes_raw + 255) / 256, n_lanes = n_chunks * 256;
             rc = ensure_workspace(&hs.ctx, n_chunks, 256);
             const size_t need = (size_t)n_lanes * (kGenFrames * 16 + kGenPathCap);
-            if (!rc && hs.ctx.scratch_bytes < need) {
-                if (hs.ctx.d_scratch) (void)hipFree(hs.ctx.d_scratch);
-                hs.ctx.d_scratch = nullptr; hs.ctx.scratch_bytes = 0;
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&hs.ctx.d_scratch), need));
-                hs.ctx.scratch_bytes = need;
-            }
+            if (!rc) HIP_TRY(hs.ctx.d_scratch.reserve(need, need));
             if (rc) return rc;
             GenArgs ga{};
-            ga.stack = reinterpret_cast<uint32_t*>(hs.ctx.d_scratch);
+            ga.stack = reinterpret_cast<uint32_t*>(hs.ctx.d_scratch.p);
             ga.path = hs.ctx.d_scratch + (size_t)n_lanes * kGenFrames * 16;
             ga.frames = kGenFrames;
             ga.path_cap = kGenPathCap;
@@ -2144,16 +2087,11 @@ int generate_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, std:
             HIP_TRY(hipStreamSynchronize(hs.stream));
             if (!(hs.ctx.h_status[0] & (kStDiverge | kStEditOverflow | kStCapacity))) {
                 // (the symbols sit in the slot's output buffer: the output gets a buffer of its own, kept by the context)
-                if (hs.ctx.gen_out_cap < total + 64) {
-                    if (hs.ctx.d_gen_out) (void)hipFree(hs.ctx.d_gen_out);
-                    hs.ctx.d_gen_out = nullptr; hs.ctx.gen_out_cap = 0;
-                    const size_t want = (size_t)total + (size_t)total / 4 + 4096;
-                    if (hipMalloc(reinterpret_cast<void**>(&hs.ctx.d_gen_out), want) != hipSuccess)
-                        return fail(TRRE_E_TOO_BIG, "error: out of device memory for the outputs of generator mode");
-                    hs.ctx.gen_out_cap = want;
-                }
+                const size_t want = (size_t)total + (size_t)total / 4 + 4096;          // (head room: grown only when total + 64 does not fit)
+                if (hs.ctx.d_gen_out.cap < total + 64 && hs.ctx.d_gen_out.reserve(want, want) != hipSuccess)
+                    return fail(TRRE_E_TOO_BIG, "error: out of device memory for the outputs of generator mode");
                 args.out = hs.ctx.d_gen_out;
-                args.cap = hs.ctx.gen_out_cap;
+                args.cap = hs.ctx.d_gen_out.cap;
                 launch_gen(2, args, ga, kGenLaneBytes, n_chunks, hs.stream);
                 HIP_TRY(hipGetLastError());
                 try {
@@ -2180,7 +2118,6 @@ int generate_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, std:
     }
     return TRRE_OK;
 }
-constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
 }  // namespace
 
 // host-only entry for the CPU test tier: the enumeration of generator mode with symbols computed elsewhere (tests/cpu_shim.cpp
@@ -2241,14 +2178,7 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
 
 // ---- ragged records (records_block.hpp) ----------------------------------------------------------------------------------
 // status word, part [tiles + 1], cnt [tiles], base [tiles + 1]
-static int rec_room(ScanCtx* cx, int64_t tiles) {
-    if (tiles <= cx->rec_tiles) return TRRE_OK;
-    (void)hipFree(cx->d_rec);
-    cx->d_rec = nullptr; cx->rec_tiles = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_rec), (size_t)(3 * tiles + 3) * 8));
-    cx->rec_tiles = tiles;
-    return TRRE_OK;
-}
+static hipError_t rec_room(ScanCtx* cx, int64_t tiles) { return cx->d_rec.reserve((size_t)tiles, (size_t)(3 * tiles + 3) * 8); }
 static void rec_carve(ScanCtx* cx, int64_t tiles, trre::RecArgs& a) {
     a.part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
     a.cnt = cx->d_rec + 2 + tiles;
@@ -2269,11 +2199,11 @@ static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     const int64_t T = rec_tile_bytes();
     const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
     const int64_t tiles = n ? (a0 + (int64_t)n + T - 1) / T : 0;
-    int rc = rec_room(cx, std::max<int64_t>(tiles, 1));
-    if (rc) return rc;
+    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
+    int rc;
     // 1. the offsets, on the device: nothing is written before they pass
     HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec), s);
+    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
     const int bad = rec_status(cx, s, nullptr, nullptr);
     if (bad < 0) return TRRE_E_DEVICE;
     if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
@@ -2283,12 +2213,7 @@ static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
         return TRRE_OK;
     }
     // 2. the staged copy (the snapshot buffer, at the input's offset mod 16, whole 16-byte vectors) and the ranks
-    if (cx->snap_bytes < n + 32) {
-        if (cx->d_snap) (void)hipFree(cx->d_snap);
-        cx->d_snap = nullptr; cx->snap_bytes = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&cx->d_snap), n + 32));
-        cx->snap_bytes = n + 32;
-    }
+    HIP_TRY(cx->d_snap.reserve(n + 32, n + 32));
     RecArgs ra{};
     ra.in_v0 = d_in - a0; ra.snap_v0 = cx->d_snap; ra.vbeg = a0; ra.vend = a0 + (int64_t)n;
     ra.off = d_off; ra.nrec = (int64_t)nrec; ra.out_off = d_out_off; ra.keep = d_in == d_out ? 1u : 0u;
@@ -2317,12 +2242,11 @@ static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     // 4. record i's output ends just past output newline number R_i
     const int64_t b0 = (int64_t)(reinterpret_cast<uintptr_t>(d_out) & 15u);
     const int64_t otiles = (b0 + (int64_t)m + T - 1) / T;
-    rc = rec_room(cx, otiles);
-    if (rc) return rc;
+    HIP_TRY(rec_room(cx, otiles));
     RecArgs oa = ra;
     oa.in_v0 = d_out - b0; oa.vbeg = b0; oa.vend = b0 + (int64_t)m;
     rec_carve(cx, otiles, oa);
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec);
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
     HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
     launch_rec_count(oa, otiles, s);
     launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
@@ -2465,7 +2389,7 @@ int scan_host_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, uin
         if (hipPointerGetAttributes(&at, static_cast<const uint8_t*>(ptr) + len - 1) != hipSuccess) { (void)hipGetLastError(); return false; }
         return at.type == hipMemoryTypeHost;
     };
-    static const bool no_direct = getenv("TRRE_NO_PINNED_DIRECT") != nullptr;      // (A/B runs)
+    const bool no_direct = trre::switches().no_pinned_direct;
     const bool in_direct = !no_direct && is_pinned(in, n), out_direct = !no_direct && cap && is_pinned(out, cap);
 
     struct Chunk { size_t off = 0, len = 0, out_at = 0, m = 0, early_at = 0; bool submitted = false, copying = false, leaving = false, early = false; CopyPool::Job job; };
@@ -2483,7 +2407,7 @@ int scan_host_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, uin
         return code;
     };
     // stage chunk k in and queue its upload + scan (and, when the output size is known beforehand, its download)
-    static const bool trace_on = getenv("TRRE_TRACE") != nullptr;
+    const bool trace_on = trre::switches().trace;
     double t_reserve = 0, t_first = 0;
     bool first_done = false;
     auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
@@ -2619,7 +2543,7 @@ struct DeviceScope {
     int prev = -1;
     hipError_t err;
     explicit DeviceScope(int device) {
-        static const bool trace_on = getenv("TRRE_TRACE") != nullptr;
+        const bool trace_on = trre::switches().trace;
         static std::atomic<bool> first{true};
         const auto t0 = std::chrono::steady_clock::now();
         err = hipGetDevice(&prev);
@@ -2748,7 +2672,7 @@ int trre_scan_host_multi(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out
     if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     int n_dev = 0;
     {
-        static const bool trace_on = getenv("TRRE_TRACE") != nullptr;
+        const bool trace_on = trre::switches().trace;
         static std::atomic<bool> first{true};
         const auto t0 = std::chrono::steady_clock::now();
         HIP_TRY(hipGetDeviceCount(&n_dev));
@@ -2762,7 +2686,7 @@ int trre_scan_host_multi(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out
     if (n == 0) return TRRE_OK;
     // TRRE_SHARDS_PER_DEVICE=k (tests): k shards per selected device, so that the sharding, the per-shard threads and
     // the reassembly run on a box with a single GPU (shards on one device take turns: calls are serialised per device)
-    static const int per_dev = getenv("TRRE_SHARDS_PER_DEVICE") ? atoi(getenv("TRRE_SHARDS_PER_DEVICE")) : 1;
+    const int per_dev = trre::switches().shards_per_device;
     if (per_dev > 1) {
         std::vector<int> rep;
         for (int d : devs) rep.insert(rep.end(), (size_t)per_dev, d);

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "launch.hpp"
+#include "switches.hpp"
 #include "scan_block.hpp"
 #include "splice_block.hpp"
 #include "one_block.hpp"
@@ -1573,7 +1574,7 @@ void launch_fb_mark(const ScanArgs& a, const FbCopyArgs& ca, const void* hdr, in
     const StreamBlobHeader& h = *static_cast<const StreamBlobHeader*>(hdr);
     constexpr int kG = kFbMarkThreads / kDirectThreads;
     // the mark form of the comb where the tables have it (TRRE_NO_FB_MARK4=1: the 8-byte comb, for A/B runs)
-    static const bool no_mark4 = getenv("TRRE_NO_FB_MARK4") != nullptr;
+    const bool no_mark4 = switches().no_fb_mark4;
     if (h.fb4_slots && !no_mark4) {
         const int lds4 = 256 + (int)((h.fb4_slots * 4u + 15u) & ~15u) + (int)h.fb4_dense * 128 + (int)((h.fb_lits * 2u + 15u) & ~15u) +
                          kFbMarkThreads * kMarkStageStride * 4 + 64 * kG;
