@@ -183,6 +183,31 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
 int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
                              size_t cap, int64_t* d_out_off, size_t* out_len, void* stream);
 
+/* Packed strings: the same packed buffer plus offsets, but record i is the CONTENT of one input line, its line end left off,
+ * which is what a column of strings holds (Arrow large_string, torch.nested values + offsets, a HF dataset column):
+ *     out_i = R(rec_i + "\n") without its last byte,
+ * R being what the reference prints for that input file.  Whatever the program prints for the line ends in exactly one
+ * framing '\n', and that byte is removed: "cat" under [a:A-z:Z] gives "CAT".  A record that itself holds '\n' bytes is several
+ * lines; their inner framing newlines stay and only the last one goes.  A NUL cuts its line.  An empty record is an empty
+ * line: its output is what the program prints for one, empty or not (':x' prints "x" under the non-deterministic engine; the
+ * reference's deterministic engine prints nothing for an empty line, whatever the program).  nrec == 0 is valid with n == 0.  The
+ * outputs are concatenated into d_out; d_out_off[i] is where record i's output starts, d_out_off[nrec] = *out_len.
+ * Arguments, overlaps, the offsets' check (TRRE_E_ARG, nothing written), scan mode only, the refusal of a program that can
+ * print a '\n' of its own (TRRE_E_UNSUPPORTED), d_in == d_out and a split-form scan in flight: as for
+ * trre_scan_device_records; d_out may be null when cap is 0.  The differences:
+ *   TRRE_E_CAPACITY  *out_len is the size of the unframed output (the framed size minus nrec).  d_out has not been written at
+ *                    all — in place the input is intact, no restore pass runs — and d_out_off is unspecified.  A retry with
+ *                    room works; cap == 0 is a size query.
+ *   TRRE_E_DIVERGES  *out_len = 0; d_out and d_out_off are unspecified; trre_last_error() holds the reference's message.
+ *                    There is no partial output here: a caller who wants the reference's takes the records call.
+ * How: the strings are expanded into a staged text with a '\n' behind each, that text is scanned as it stands into a buffer
+ * of the library's own, and the framed output is compacted into d_out without each record's closing '\n'.
+ * Device memory, kept by the (prog, device) until trre_free: the staged text, n + nrec + 64 bytes; the framed output,
+ * cap + nrec + 64 bytes; 24 bytes per 16 KiB of staged text and per 64 KiB of framed output.  Synchronous with respect to
+ * `stream`. */
+int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
+                             size_t cap, int64_t* d_out_off, size_t* out_len, void* stream);
+
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */
 #define TRRE_SCAN_GUARD_UNDECIDED 1u /* NFT engine: the input holds a line long enough to exhaust the reference's 65 536-item stack

@@ -93,6 +93,7 @@ def lib():
         L.trre_export_guided_tables.restype = sz
         L.trre_scan_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
         L.trre_scan_device_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
+        L.trre_scan_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -255,8 +256,45 @@ class Program:
         _check(rc)
         return out[:m.value], out_offsets
 
+    def scan_strings(self, values, offsets, out=None, out_offsets=None, stream=None):
+        """Packed strings (trre_scan_device_strings): values, a 1-D uint8 CUDA tensor, holds string i at
+        values[offsets[i]:offsets[i+1]] (offsets: 1-D int64 CUDA tensor, nrec + 1 entries, from 0 to values.numel()).  Each
+        string is the content of one line, without a line end: its output is what the program prints for that line, without
+        the framing newline (b"cat" under [a:A-z:Z] gives b"CAT"; an empty string gives what an empty line prints).  Returns
+        (out_values, out_offsets): string i's output is out_values[out_offsets[i]:out_offsets[i+1]].  out may be values itself
+        (in place); a too small out is replaced.  A string the reference does not survive raises TrreError with partial=None."""
+        import torch
+        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
+        n, nrec = values.numel(), offsets.numel() - 1
+        if out is None:
+            out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
+        if out_offsets is None:
+            out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
+        m = ctypes.c_size_t()
+
+        def call(o):
+            return lib().trre_scan_device_strings(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o.data_ptr(), o.numel(),
+                                                  out_offsets.data_ptr(), ctypes.byref(m), s)
+        with torch.cuda.device(values.device):
+            rc = call(out)
+            if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
+                out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
+                rc = call(out)
+        _check(rc)
+        return out[:m.value], out_offsets
+
+    def map_strings(self, records, device=0):
+        """list of bytes in -> list of bytes out, the program applied to each string as one line (through scan_strings)"""
+        return self._map_list(records, device, self.scan_strings)
+
     def scan_list(self, records, device=0):
         """list of bytes in -> list of bytes out, each record scanned as a file of its own (through scan_records)"""
+        return self._map_list(records, device, self.scan_records)
+
+    @staticmethod
+    def _map_list(records, device, scan):
         import numpy as np
         import torch
         recs = [_bytes(r) for r in records]
@@ -265,7 +303,7 @@ class Program:
         dev = torch.device("cuda", device)
         packed = b"".join(recs)
         values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
-        out, out_off = self.scan_records(values, torch.from_numpy(off).to(dev))
+        out, out_off = scan(values, torch.from_numpy(off).to(dev))
         blob = out.cpu().numpy().tobytes()
         o = out_off.cpu().numpy().tolist()
         return [blob[o[i]:o[i + 1]] for i in range(len(recs))]

@@ -12,6 +12,7 @@ struct LazyArgs;
 struct OneArgs;
 struct MapGenArgs;
 struct RecArgs;
+struct StrArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -86,6 +87,14 @@ void launch_rec_rank(const RecArgs& a, void* stream);
 void launch_rec_count(const RecArgs& a, int64_t tiles, void* stream);
 void launch_rec_locate(const RecArgs& a, int64_t tiles, uint32_t* status, void* stream);
 void launch_rec_restore(const RecArgs& a, uint8_t* dst, void* stream);
+// packed strings (records_block.hpp): bytes per tile; the first record of every tile (side 0: by the staged position of its
+// closing '\n', 1: by the framed position); the staged text, its '\n' per tile and the tile-local ranks; the ranks; the
+// compaction of the framed output into the caller's buffer, with the final offsets
+int64_t str_tile_bytes();
+void launch_str_part(int side, const StrArgs& a, int64_t* part, int64_t tiles, void* stream);
+void launch_str_stage(const StrArgs& a, int64_t tiles, void* stream);
+void launch_str_rank(const StrArgs& a, void* stream);
+void launch_str_unframe(const StrArgs& a, int64_t tiles, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

@@ -282,4 +282,235 @@ TRRE_HD void rec_restore(const RecArgs& a, uint8_t* dst, int64_t i) {
     if (p > a.off[i]) dst[p - 1] = (uint8_t)((uint64_t)a.out_off[i + 1] >> 56);
 }
 
+// ---- packed strings (trre_scan_device_strings) ----------------------------------------------------------------------------
+// Record i is the content of ONE line with its line end left off: out_i = R(rec_i + '\n') minus the framing '\n' that closes
+// it.  The STAGED text holds in[off[i] .. off[i+1]) at off[i] + i and a '\n' at key(i) = off[i+1] + i; it is n + nrec bytes,
+// key is strictly increasing, and the plain scan of it is the concatenation of the records' framed outputs.  Record i's framed
+// output ends just past output newline number
+//     R_i = number of '\n' in staged[0, key(i)] = (number of '\n' in in[0, off[i+1])) + i + 1
+// and the byte at framed position t of record i goes to t - i, its closing '\n' nowhere.  The passes:
+//   k_rec_check     the offsets (as above)
+//   k_str_part(0)   the first record of every staged tile: the first i with key(i) >= b * TILE
+//   k_str_stage     an expansion: input range of the tile -> LDS -> whole staged vectors; the tile's '\n'; the tile-local R_i
+//   k_chunk_scan, k_str_rank   R_i = tile base + local rank, in out_off[i + 1]
+//   (the plain scan of the staged text into the context's framed buffer)
+//   k_rec_count, k_chunk_scan, k_rec_part(1), k_rec_locate   out_off[i + 1] = position just past framed newline R_i (as above)
+//   k_str_part(1)   the first record of every framed tile: the first i with out_off[i + 1] - 1 >= b * TILE
+//   k_str_unframe   a compaction: framed tile -> LDS -> d_out (output-parallel); the tile that holds record i's closing '\n'
+//                   is the only reader of out_off[i + 1] in this pass and writes its final value, out_off[i + 1] - (i + 1)
+// Both buffers the tiles are over (staged, framed) are the context's, 16-byte aligned, with whole vectors behind the end.  A tile
+// keeps its BYTES in LDS (TILE + 32), a bit per byte for the record ends in it, the ends before every vector (pv) and, for the
+// compaction, the source vector each destination vector starts in (inv): about 25 KiB for the device's 16 KiB tiles.
+constexpr int kStrVecs = 4;                           // 16-byte vectors per thread: 16 KiB tiles
+using StrGeoDev = RecGeo<kRecThreads, kStrVecs>;
+
+struct StrArgs {
+    const uint8_t* src_v0;  // stage: the caller's input - vbeg (16-byte aligned); unframe: the framed output (aligned)
+    int64_t vbeg;           // stage: the input's address mod 16
+    int64_t total;          // bytes of the space the tiles are over: n + nrec (staged) / the framed length
+    uint8_t* dst;           // stage: the staged text (aligned); unframe: the caller's d_out (any alignment)
+    int64_t dst_len;        // unframe: framed length - nrec; nothing is stored at or behind it
+    const int64_t* off;     // [nrec + 1] the caller's offsets (stage)
+    int64_t nrec;
+    int64_t* out_off;       // [nrec + 1] ranks, located positions, then the output offsets
+    const int64_t* part;    // [tiles + 1] first record of each tile
+    uint64_t* cnt;          // [tiles] '\n' per staged tile
+    const uint64_t* base;   // [tiles + 1] exclusive scan of cnt
+};
+
+struct StrStageKey {   // staged position of record i's closing '\n'
+    const int64_t* off;
+    TRRE_HD int64_t operator()(int64_t i) const { return off[i + 1] + i; }
+};
+struct StrFramedKey {  // framed position of record i's closing '\n'
+    const int64_t* out_off;
+    TRRE_HD int64_t operator()(int64_t i) const { return out_off[i + 1] - 1; }
+};
+// k_str_part: part[b] = the first record whose closing '\n' lies in tile b or after it (b in [0, tiles])
+TRRE_HD void str_part(const StrArgs& a, int64_t* part, int64_t tile, int side, int64_t b) {
+    part[b] = side == 0 ? rec_lower_bound(StrStageKey{a.off}, a.nrec, b * tile) : rec_lower_bound(StrFramedKey{a.out_off}, a.nrec, b * tile);
+}
+
+// 16 bytes from byte index s of an LDS image of whole vectors: two aligned vectors, funnel-shifted (the vector behind is
+// read even when s is aligned: the image has one to spare)
+TRRE_HD U128 str_funnel16(const U128* lds, int64_t s) {
+    const U128 lo = lds[s >> 4], hi = lds[(s >> 4) + 1];
+    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t sh = (uint32_t)s & 15u;
+    if (sh & 8u) { w[0] = w[2]; w[1] = w[3]; w[2] = w[4]; w[3] = w[5]; w[4] = w[6]; w[5] = w[7]; }
+    if (sh & 4u) { w[0] = w[1]; w[1] = w[2]; w[2] = w[3]; w[3] = w[4]; w[4] = w[5]; }
+    const uint32_t bs = (sh & 3u) * 8u;
+    U128 r;
+    r.x = (uint32_t)((((uint64_t)w[1] << 32) | w[0]) >> bs); r.y = (uint32_t)((((uint64_t)w[2] << 32) | w[1]) >> bs);
+    r.z = (uint32_t)((((uint64_t)w[3] << 32) | w[2]) >> bs); r.w = (uint32_t)((((uint64_t)w[4] << 32) | w[3]) >> bs);
+    return r;
+}
+TRRE_HD void str_put_byte(U128& r, int k, uint32_t c) {
+    uint32_t& w = k < 4 ? r.x : k < 8 ? r.y : k < 12 ? r.z : r.w;
+    w |= c << (8u * (uint32_t)(k & 3));
+}
+
+// the tile's source: stage — the input range [s0 - i0, s1 - i1) as whole vectors of the input's v-space, `shift` bytes in
+// front; unframe — the framed tile itself
+template <class G>
+struct StrTile {
+    int64_t s0, s1;      // the tile in its space
+    int64_t i0, i1;      // records whose closing '\n' lies in it
+    int64_t v0, vend;    // source vectors from v0 (16-byte aligned), loaded while below vend
+    int shift;           // LDS byte index of the tile's first source byte
+    TRRE_HD StrTile(const StrArgs& a, int64_t b, bool stage) {
+        s0 = b * G::TILE;
+        s1 = s0 + G::TILE < a.total ? s0 + G::TILE : a.total;
+        i0 = a.part[b]; i1 = a.part[b + 1];
+        if (stage) {
+            const int64_t p = s0 - i0 + a.vbeg;
+            v0 = p & ~(int64_t)15; shift = (int)(p & 15); vend = s1 - i1 + a.vbeg;
+        } else {
+            v0 = s0; shift = 0; vend = s1;
+        }
+    }
+};
+// the thread's source vectors (vector k = j * THREADS + tid: coalesced; thread 0 takes the one more that a shift needs)
+template <class G>
+TRRE_HD void str_load_vecs(const StrArgs& a, const StrTile<G>& t, int tid, U128 (&w)[G::VECS + 1]) {
+    for (int j = 0; j <= G::VECS; ++j) {
+        const int k = j * G::THREADS + tid;
+        if (j == G::VECS && tid != 0) break;
+        const int64_t v = t.v0 + 16 * (int64_t)k;
+        if (v < t.vend) w[j] = rec_load16(a.src_v0 + v);
+    }
+}
+template <class G>
+TRRE_HD void str_keep_vecs(const StrTile<G>& t, int tid, const U128 (&w)[G::VECS + 1], U128* lds) {
+    for (int j = 0; j <= G::VECS; ++j) {
+        const int k = j * G::THREADS + tid;
+        if (j == G::VECS && tid != 0) break;
+        if (t.v0 + 16 * (int64_t)k < t.vend) lds[k] = w[j];
+    }
+}
+// a bit per closing '\n' of the tile (bits32: TILE / 32 words, zeroed before).  stage: from the offsets.  unframe: from the
+// located positions, which the owning tile replaces by the final offsets here
+template <class G>
+TRRE_HD void str_mark(const StrArgs& a, const StrTile<G>& t, int tid, uint32_t* bits32, bool stage) {
+    for (int64_t i = t.i0 + tid; i < t.i1; i += G::THREADS) {
+        int64_t x;
+        if (stage) {
+            x = a.off[i + 1] + i - t.s0;
+        } else {
+            const int64_t e = a.out_off[i + 1];
+            x = e - 1 - t.s0;
+            a.out_off[i + 1] = e - (i + 1);
+        }
+        if (x >= 0 && x < t.s1 - t.s0) TRRE_REC_LDS_OR(bits32 + (x >> 5), 1u << (uint32_t)(x & 31));
+    }
+}
+// marks before each of the thread's segment vectors (pre_t: before the segment); pv[NVEC] = the tile's marks
+template <class G>
+TRRE_HD void str_fill_pv(const uint16_t* bits16, uint32_t pre_t, int tid, uint32_t* pv) {
+    uint32_t run = pre_t;
+    for (int k = 0; k < G::VECS; ++k) {
+        pv[tid * G::VECS + k] = run;
+        run += rec_popc(bits16[tid * G::VECS + k]);
+    }
+    if (tid == G::THREADS - 1) pv[G::NVEC] = run;
+}
+// k_str_stage: the thread's staged vectors out (vector q = j * THREADS + tid), and in place of each vector's marks its '\n'
+// mask (valid bytes only).  A vector without a mark is 16 consecutive source bytes.
+template <class G>
+TRRE_HD void str_stage_vecs(const StrArgs& a, const StrTile<G>& t, int tid, const U128* lds, uint16_t* bits16, const uint32_t* pv) {
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(lds);
+    for (int j = 0; j < G::VECS; ++j) {
+        const int q = j * G::THREADS + tid;
+        const int64_t s = t.s0 + 16 * (int64_t)q;
+        if (s >= t.s1) { bits16[q] = 0; continue; }
+        const uint32_t mk = bits16[q];
+        const int64_t sb = t.shift + 16 * (int64_t)q - pv[q];
+        U128 r;
+        if (mk == 0) {
+            r = str_funnel16(lds, sb);
+        } else {
+            r.x = r.y = r.z = r.w = 0;
+            int64_t at = sb;
+            for (int k = 0; k < 16 && s + k < t.s1; ++k) str_put_byte(r, k, (mk >> k) & 1u ? (uint32_t)'\n' : bytes[at++]);
+        }
+        rec_store16(a.dst + s, r);
+        bits16[q] = (uint16_t)(rec_nl16(r) & rec_valid16(s, 0, t.s1));
+    }
+}
+// ... the tile-local rank of every record whose closing '\n' lies in the tile, into out_off[i + 1]
+template <class G>
+TRRE_HD void str_rank_records(const StrArgs& a, const StrTile<G>& t, int tid, const uint16_t* bits16, const uint32_t* pre) {
+    for (int64_t i = t.i0 + tid; i < t.i1; i += G::THREADS)
+        a.out_off[i + 1] = (int64_t)rec_rank_at<G>(bits16, pre, a.off[i + 1] + i - t.s0);
+}
+// k_str_rank: the tile's base onto record i's local rank
+TRRE_HD void str_add_base(const StrArgs& a, int64_t tile, int64_t i) {
+    a.out_off[i + 1] = (int64_t)((uint64_t)a.out_off[i + 1] + a.base[(a.off[i + 1] + i) / tile]);
+}
+
+// k_str_unframe.  The tile's E = (s1 - s0) - marks kept bytes go to dst + d0, d0 = s0 - i0.  Destination vectors are those of
+// the ADDRESS: vector g holds kept bytes [e0(g), e1(g)), e0 = 16 g - A (0 for g = 0), A = (address of dst + d0) mod 16, so that
+// every whole one is an aligned 16-byte store and the ragged first and last, which neighbours share, are byte stores.
+template <class G>
+struct StrOut {
+    int64_t d0, E;
+    int A, ng;
+    TRRE_HD StrOut(const StrArgs& a, const StrTile<G>& t, uint32_t marks) {
+        d0 = t.s0 - t.i0;
+        E = t.s1 - t.s0 - (int64_t)marks;
+        A = (int)((reinterpret_cast<uintptr_t>(a.dst) + (uintptr_t)d0) & 15u);
+        ng = E ? (int)((E + A + 15) >> 4) : 0;
+    }
+    TRRE_HD int64_t e0(int g) const { return g ? 16 * (int64_t)g - A : 0; }
+};
+// inv[g] = the source vector that holds kept byte e0(g): source vector q holds kept bytes [lo, hi), at most one e0 of each kind
+template <class G>
+TRRE_HD void str_fill_inv(const StrTile<G>& t, const StrOut<G>& o, int tid, const uint16_t* bits16, const uint32_t* pv, uint16_t* inv) {
+    for (int j = 0; j < G::VECS; ++j) {
+        const int q = j * G::THREADS + tid;
+        const int64_t left = t.s1 - t.s0 - 16 * (int64_t)q;
+        if (left <= 0) continue;
+        const int64_t lo = 16 * (int64_t)q - pv[q];
+        const int64_t hi = lo + (left < 16 ? left : 16) - rec_popc(bits16[q]);
+        if (hi <= lo) continue;
+        if (lo == 0) inv[0] = (uint16_t)q;
+        const int64_t g = (lo + o.A + 15) >> 4, e = 16 * g - o.A;
+        if (g >= 1 && e < hi) inv[g] = (uint16_t)q;
+    }
+}
+template <class G>
+TRRE_HD void str_unframe_vecs(const StrArgs& a, const StrTile<G>& t, const StrOut<G>& o, int tid, const U128* lds, const uint16_t* bits16,
+                              const uint32_t* pv, const uint16_t* inv) {
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(lds);
+    for (int g = tid; g < o.ng; g += G::THREADS) {
+        const int64_t e0 = o.e0(g);
+        const int64_t e1 = 16 * (int64_t)g - o.A + 16 < o.E ? 16 * (int64_t)g - o.A + 16 : o.E;
+        if (o.d0 + e1 > a.dst_len) continue;                               // (never: the offsets were checked end to end before)
+        const int q = inv[g];
+        uint32_t um = ~(uint32_t)bits16[q] & 0xffffu;                      // kept bytes of the source vector
+        for (int64_t r = e0 - (16 * (int64_t)q - pv[q]); r > 0; --r) um &= um - 1u;
+        const int px = __builtin_ctz(um | 0x10000u);
+        int64_t x = 16 * (int64_t)q + px;
+        uint8_t* d = a.dst + o.d0 + e0;
+        const bool whole = e1 - e0 == 16;
+        const uint32_t ahead = ((uint32_t)bits16[q] | (q + 1 < G::NVEC ? (uint32_t)bits16[q + 1] << 16 : 0u)) >> px;
+        if (whole && (ahead & 0xffffu) == 0) {
+            rec_store16(d, str_funnel16(lds, x));
+        } else if (whole) {
+            U128 r;
+            r.x = r.y = r.z = r.w = 0;
+            for (int k = 0; k < 16; ++k) {
+                while ((bits16[x >> 4] >> (x & 15)) & 1u) ++x;
+                str_put_byte(r, k, bytes[x++]);
+            }
+            rec_store16(d, r);
+        } else {
+            for (int64_t e = e0; e < e1; ++e) {
+                while ((bits16[x >> 4] >> (x & 15)) & 1u) ++x;
+                *d++ = bytes[x++];
+            }
+        }
+    }
+}
+
 }  // namespace trre

@@ -165,9 +165,10 @@ struct ScanCtx {
     DevBuf<uint32_t> d_redo;          // window kernel redo list (lanes)
     DevBuf<uint8_t> d_sym;            // guided families: one symbol per input byte (bytes)
     DevBuf<uint8_t> d_snap;           // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads;
-                                      // trre_scan_device_records: the staged copy, which the scan reads (bytes)
+                                      // trre_scan_device_records / _strings: the staged copy, which the scan reads (bytes)
     DevBuf<uint64_t> d_rec;           // trre_scan_device_records: status word, then part [tiles + 1], cnt [tiles], base [tiles + 1] (tiles)
     DevBuf<uint8_t> d_gen_out;        // generator modes: the enumeration's output before it goes down (bytes)
+    DevBuf<uint8_t> d_framed;         // trre_scan_device_strings: the scan's output with every record's closing '\n' still in it (bytes)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
     DevBuf<uint32_t> d_cevents, d_chdr;
@@ -2280,6 +2281,106 @@ int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const 
     std::lock_guard<std::mutex> lock(st->mu);
     if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
     return records_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
+}
+
+// ---- packed strings (records_block.hpp) ------------------------------------------------------------------------------------
+// d_rec, string tiles (16 KiB): status word, part [tiles + 1], cnt [tiles], base [tiles + 1]
+static int strings_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
+                      size_t cap, int64_t* d_out_off, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    const int64_t T = str_tile_bytes();
+    const int64_t total = (int64_t)(n + nrec);                     // the staged text
+    const int64_t tiles = (total + T - 1) / T;
+    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
+    int rc;
+    // 1. the offsets, on the device: nothing is written before they pass
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
+    const int bad = rec_status(cx, s, nullptr, nullptr);
+    if (bad < 0) return TRRE_E_DEVICE;
+    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 2. the staged text (the snapshot buffer, 16-byte aligned, whole vectors) and the ranks
+    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    StrArgs sa{};
+    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
+    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = d_out_off;
+    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
+    launch_str_part(0, sa, part, tiles, s);
+    launch_str_stage(sa, tiles, s);
+    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    launch_str_rank(sa, s);
+    // 3. the plain scan of the staged text into the framed buffer, family as chosen for the program
+    const size_t fcap = cap + nrec;
+    HIP_TRY(cx->d_framed.reserve(fcap + 64, fcap + 64));
+    rc = enqueue(p, st, cx, scan_family(*p), cx->d_snap, (size_t)total, cx->d_framed, fcap, s);
+    if (rc) { cx->pend = Pending(); return rc; }
+    size_t m = 0;
+    rc = finish(p, st, cx, &m);
+    if (rc == TRRE_E_CAPACITY && out_len) *out_len = m >= nrec ? m - nrec : 0;
+    if (rc) return rc;                                     // (TRRE_E_DIVERGES: *out_len stays 0)
+    if (m < nrec) return fail(TRRE_E_DEVICE, "error: the strings' output offsets do not add up (internal)");
+    // 4. record i's framed output ends just past framed newline number R_i
+    const int64_t RT = rec_tile_bytes();
+    const int64_t otiles = ((int64_t)m + RT - 1) / RT;
+    HIP_TRY(rec_room(cx, otiles));
+    RecArgs oa{};
+    oa.in_v0 = cx->d_framed; oa.vbeg = 0; oa.vend = (int64_t)m; oa.nrec = (int64_t)nrec; oa.out_off = d_out_off;
+    rec_carve(cx, otiles, oa);
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_count(oa, otiles, s);
+    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
+    launch_rec_part(1, oa, otiles, s);
+    launch_rec_locate(oa, otiles, d_bad, s);
+    uint64_t last = 0;
+    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(d_out_off + nrec), &last);
+    if (lost < 0) return TRRE_E_DEVICE;
+    if (lost || last != m) return fail(TRRE_E_DEVICE, "error: the strings' output offsets do not add up (internal)");
+    // 5. the framed output without the closing newlines into the caller's buffer, and the final offsets
+    const int64_t utiles = ((int64_t)m + T - 1) / T;
+    HIP_TRY(rec_room(cx, utiles));
+    StrArgs ua{};
+    ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - nrec);
+    ua.nrec = (int64_t)nrec; ua.out_off = d_out_off;
+    part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    ua.part = part;
+    launch_str_part(1, ua, part, utiles, s);
+    launch_str_unframe(ua, utiles, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_len) *out_len = m - nrec;
+    return TRRE_OK;
+}
+
+int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                             int64_t* d_out_off, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (!p || !d_off || !d_out_off || (n && !d_in) || (cap && !d_out)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_SCAN)
+        return fail(TRRE_E_UNSUPPORTED, "error: strings are offered in scan mode only (a line of -m, -a, -ma prints zero or many newlines)");
+    if (p->prints_newline)
+        return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: record outputs could not be told apart");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
+    const size_t ob = (nrec + 1) * 8;
+    if (ranges_overlap(d_off, ob, d_out_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
+        ranges_overlap(d_out_off, ob, d_in, n) || ranges_overlap(d_out_off, ob, d_out, cap))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or the other offsets array");
+    DeviceState* st;
+    int rc = current_state(p, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return strings_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
 }
 
 namespace {

@@ -14,6 +14,8 @@
 //                 emitted into an LDS staging tile, coalesced copy-out.
 //   k_rec_*       ragged records (trre_scan_device_records): staging, ranks and
 //                 per-record output offsets around the plain scan (records_block.hpp).
+//   k_str_*       packed strings (trre_scan_device_strings): the strings expanded into
+//                 lines before the plain scan, the framing newlines compacted away after it.
 //
 // The per-thread phase bodies live in scan_block.hpp / scan_core.hpp.
 #include <hip/hip_runtime.h>
@@ -1821,6 +1823,72 @@ __global__ __launch_bounds__(256) void k_rec_restore(RecArgs a, uint8_t* dst) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) rec_restore(a, dst, i);
 }
 
+// ---- packed strings (records_block.hpp; runtime.cpp: trre_scan_device_strings) ---------------------------------------------
+using SG = StrGeoDev;
+static_assert(SG::THREADS == RG::THREADS, "rec_block_scan");
+
+__global__ __launch_bounds__(256) void k_str_part(StrArgs a, int64_t* part, int64_t tiles, int side) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b <= tiles) str_part(a, part, SG::TILE, side, b);
+}
+
+__global__ __launch_bounds__(SG::THREADS) void k_str_stage(StrArgs a) {
+    __shared__ U128 lds[SG::NVEC + 2];
+    __shared__ uint32_t bits32[SG::NVEC / 2];
+    __shared__ uint32_t pv[SG::NVEC + 1];
+    __shared__ uint32_t pre[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const StrTile<SG> t(a, blockIdx.x, true);
+    U128 w[SG::VECS + 1];
+    str_load_vecs<SG>(a, t, tid, w);                 // the tile's source bytes are on their way while the record ends are looked up
+    for (int k = tid; k < SG::NVEC / 2; k += SG::THREADS) bits32[k] = 0;
+    __syncthreads();
+    str_mark<SG>(a, t, tid, bits32, true);
+    str_keep_vecs<SG>(t, tid, w, lds);
+    __syncthreads();
+    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
+    rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
+    str_fill_pv<SG>(bits16, pre[tid], tid, pv);
+    __syncthreads();
+    str_stage_vecs<SG>(a, t, tid, lds, bits16, pv);
+    __syncthreads();
+    const uint32_t total = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
+    if (tid == 0) a.cnt[blockIdx.x] = total;
+    str_rank_records<SG>(a, t, tid, bits16, pre);
+}
+
+__global__ __launch_bounds__(256) void k_str_rank(StrArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) str_add_base(a, SG::TILE, i);
+}
+
+__global__ __launch_bounds__(SG::THREADS) void k_str_unframe(StrArgs a) {
+    __shared__ U128 lds[SG::NVEC + 2];
+    __shared__ uint32_t bits32[SG::NVEC / 2];
+    __shared__ uint32_t pv[SG::NVEC + 1];
+    __shared__ uint16_t inv[SG::NVEC + 2];
+    __shared__ uint32_t pre[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const StrTile<SG> t(a, blockIdx.x, false);
+    U128 w[SG::VECS + 1];
+    str_load_vecs<SG>(a, t, tid, w);
+    for (int k = tid; k < SG::NVEC / 2; k += SG::THREADS) bits32[k] = 0;
+    __syncthreads();
+    str_mark<SG>(a, t, tid, bits32, false);
+    str_keep_vecs<SG>(t, tid, w, lds);
+    __syncthreads();
+    const uint16_t* bits16 = reinterpret_cast<const uint16_t*>(bits32);
+    const uint32_t marks = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
+    str_fill_pv<SG>(bits16, pre[tid], tid, pv);
+    __syncthreads();
+    const StrOut<SG> o(a, t, marks);
+    str_fill_inv<SG>(t, o, tid, bits16, pv, inv);
+    __syncthreads();
+    str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
+}
+
 unsigned rec_grid(int64_t items) {
     const int64_t blocks = (items + 255) / 256;
     return (unsigned)(blocks < 1 ? 1 : blocks > 256 * 16 ? 256 * 16 : blocks);
@@ -1847,6 +1915,19 @@ void launch_rec_locate(const RecArgs& a, int64_t tiles, uint32_t* status, void* 
 }
 void launch_rec_restore(const RecArgs& a, uint8_t* dst, void* stream) {
     hipLaunchKernelGGL(k_rec_restore, dim3(rec_grid(a.nrec)), dim3(256), 0, static_cast<hipStream_t>(stream), a, dst);
+}
+int64_t str_tile_bytes() { return SG::TILE; }
+void launch_str_part(int side, const StrArgs& a, int64_t* part, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_str_part, dim3((unsigned)((tiles + 1 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a, part, tiles, side);
+}
+void launch_str_stage(const StrArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_str_stage, dim3((unsigned)tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_str_rank(const StrArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_str_rank, dim3(rec_grid(a.nrec)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_str_unframe(const StrArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_str_unframe, dim3((unsigned)tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
 }
 
 }  // namespace trre
