@@ -11,19 +11,9 @@
 #include "one_block.hpp"
 #include "map_block.hpp"
 #include "device_blob.hpp"
+#include "pass_block.hpp"
 
 namespace trre {
-namespace {
-
-constexpr int kWave = 64;
-constexpr int kLdsLimit = 160 * 1024;
-
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-    for (int d = 32; d; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, kWave);
-    return v;
-}
-
-}  // namespace
 
 // ---- memoryless programs of any output length: one pass, no state (map_block.hpp) ---------------------------------------------------
 // The two-level look-back of k_stream_one without the exit rows, in groups of 64: a tile publishes its total (descriptor) and adds it to its

@@ -32,55 +32,10 @@
 #include "lazy_block.hpp"
 #include "guard_block.hpp"
 #include "records_block.hpp"
+#include "pass_block.hpp"
 
 namespace trre {
 namespace {
-
-constexpr int kWave = 64;
-
-// Kernels that take more than 64 KiB of dynamic LDS need the limit raised — once per kernel and device, not per launch
-// (a launch is ~5 us of host time; the call is another 2-3): the limit is set to the CU's whole 160 KiB.
-constexpr int kLdsLimit = 160 * 1024;
-template <auto Kernel>
-void allow_big_lds() {
-    static std::atomic<uint64_t> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_relaxed) & bit) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    done.fetch_or(bit, std::memory_order_relaxed);
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-    for (int d = 32; d; d >>= 1) v = min(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-    for (int d = 32; d; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-    for (int d = 32; d; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, kWave);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-    for (int d = 32; d; d >>= 1) {
-        uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, kWave);
-        uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, kWave);
-        v += (uint64_t)hi << 32 | lo;
-    }
-    return v;
-}
-// inclusive scan inside a wave
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
-    const int lane = threadIdx.x & (kWave - 1);
-    for (int d = 1; d < kWave; d <<= 1) {
-        uint32_t u = (uint32_t)__shfl_up((int)v, d, kWave);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 
 // LDS carve shared by the tile kernels
 template <class G, class Engine>
@@ -150,21 +105,8 @@ __global__ __launch_bounds__(G::THREADS) void k_scan_count(ScanArgs a) {
     CountSink sink;
     uint32_t st = 0;
     lane_walk_gen<G, Engine>(a, T, L, v0, tin, tid, sink, st);
-    if (sink.n > 0xffffffffull) { st |= kStCapacity; sink.n = 0xffffffffull; }
-    a.lane_counts[(size_t)blockIdx.x * G::THREADS + tid] = (uint32_t)sink.n;
-
-    const uint64_t wsum = wave_sum(sink.n);
-    st = wave_or(st);
-    if ((tid & (kWave - 1)) == 0) {
-        part[tid / kWave] = wsum;
-        if (st) atomicOr(a.status, st);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < G::THREADS / kWave; ++w) t += part[w];
-        a.chunk_total[blockIdx.x] = t;
-    }
+    pass_count_epilogue<G::THREADS>(a, blockIdx.x, tid, true, part, sink.n, st);
+    pass_publish(a.status, st);
 }
 
 // exclusive scan of chunk_total[0..n) into chunk_base[0..n], chunk_base[n] = total
@@ -203,17 +145,11 @@ __global__ __launch_bounds__(G::THREADS) void k_scan_emit(ScanArgs a) {
     tile_load<G>(a, v0, tin, tid);
 
     // lane offsets: workgroup-wide exclusive scan of the counts from pass 1
-    const uint32_t mine = a.lane_counts[(size_t)blockIdx.x * G::THREADS + tid];
-    const uint32_t incl = wave_scan_incl(mine);
-    if ((tid & (kWave - 1)) == kWave - 1) wpart[tid / kWave] = incl;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < tid / kWave; ++w) wbase += wpart[w];
-    const uint64_t lane_base = (uint64_t)wbase + incl - mine;
     const uint64_t total = a.chunk_total[blockIdx.x];
     const uint64_t gbase = a.chunk_base[blockIdx.x];
-    if (gbase + total > a.cap) {                       // uniform for the workgroup
-        if (tid == 0) atomicOr(a.status, kStCapacity);
+    const uint64_t lane_base = pass_emit_base<G::THREADS>(a, blockIdx.x, tid, true, wpart) - gbase;
+    if (pass_over_capacity(a, blockIdx.x)) {           // uniform for the workgroup
+        pass_publish(a.status, kStCapacity);
         return;
     }
     const int shift = (int)((reinterpret_cast<uintptr_t>(a.out) + gbase) & 15u);
@@ -224,8 +160,7 @@ __global__ __launch_bounds__(G::THREADS) void k_scan_emit(ScanArgs a) {
     ByteSink sink{staged ? tout + shift + lane_base : a.out + gbase + lane_base};
     uint32_t st = 0;
     lane_walk_gen<G, Engine>(a, T, L, v0, tin, tid, sink, st);
-    st = wave_or(st);
-    if (st && (tid & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
     if (staged) {
         __syncthreads();
         tile_store_seq<G>(a.out + gbase, tout, shift, (int64_t)total, tid);
@@ -284,17 +219,10 @@ __global__ __launch_bounds__(kDirectThreads) void k_stream_direct(ScanArgs a, in
     // (a bounded fold that overflowed in the count pass: the launch is void, finish() runs the buffer on another family)
     if (kMode == 2 && !a.lp_emit && (*a.status & kStOverflow)) return;
     if (kMode == 2 && !a.lp_emit) {
-        // lane offsets: workgroup-wide exclusive scan of the counts from the count launch
         uint32_t* wpart = reinterpret_cast<uint32_t*>(smem + kLds - kDirectWsc - 64);
-        const uint32_t mine = a.lane_counts[lane];
-        const uint32_t incl = wave_scan_incl(mine);
-        if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[threadIdx.x / kWave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < (int)threadIdx.x / kWave; ++w) wbase += wpart[w];
-        base = a.chunk_base[blockIdx.x] + wbase + incl - mine;
-        if (a.chunk_base[blockIdx.x] + a.chunk_total[blockIdx.x] > a.cap) {
-            if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+        base = pass_emit_base<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, wpart);
+        if (pass_over_capacity(a, blockIdx.x)) {               // (uniform for the workgroup)
+            pass_publish(a.status, kStCapacity);
             return;
         }
     }
@@ -305,19 +233,9 @@ __global__ __launch_bounds__(kDirectThreads) void k_stream_direct(ScanArgs a, in
     if (kMode == 1 && kSym && (st & kStDiverge)) atomicMax(a.status + 1, 0xffffffffu - (uint32_t)lane);
     if (kMode == 1) {
         uint64_t* part = reinterpret_cast<uint64_t*>(smem + kLds - kDirectWsc - 64);
-        if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-        a.lane_counts[lane] = (uint32_t)L.count;
-        const uint64_t wsum = wave_sum(L.count);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = wsum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < kDirectThreads / kWave; ++w) t += part[w];
-            a.chunk_total[blockIdx.x] = t;
-        }
+        pass_count_epilogue<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, part, L.count, st);
     }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
 }
 
 // Count / emit passes over the 16-byte entries of a small table (front.hpp): the whole table in LDS.
@@ -391,8 +309,7 @@ __global__ __launch_bounds__(kDirectThreads) void k_stream_g16(ScanArgs a, int64
                     continue;
                 }
                 g16_lane<1, kSym, kHasSlow>(a, T, h.n_cls, j, lane_bytes, ring, 0, Lj, st);
-                if (Lj.count > 0xffffffffull) { st |= kStCapacity; Lj.count = 0xffffffffull; }
-                a.lane_counts[j] = (uint32_t)Lj.count;
+                pass_count_store(a, j, Lj.count, st);
                 if (kSym != 0 && (st & kStDiverge)) atomicMax(a.status + 1, 0xffffffffu - (uint32_t)j);
                 state = a.exit_rows[j];
                 ++j;
@@ -406,15 +323,9 @@ __global__ __launch_bounds__(kDirectThreads) void k_stream_g16(ScanArgs a, int64
     } else
     if (kMode == 2 && !a.lp_emit) {
         uint32_t* wpart = reinterpret_cast<uint32_t*>(tail);
-        const uint32_t mine = a.lane_counts[lane];
-        const uint32_t incl = wave_scan_incl(mine);
-        if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[threadIdx.x / kWave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < (int)threadIdx.x / kWave; ++w) wbase += wpart[w];
-        base = a.chunk_base[blockIdx.x] + wbase + incl - mine;
-        if (a.chunk_base[blockIdx.x] + a.chunk_total[blockIdx.x] > a.cap) {
-            if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+        base = pass_emit_base<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, wpart);
+        if (pass_over_capacity(a, blockIdx.x)) {               // (uniform for the workgroup)
+            pass_publish(a.status, kStCapacity);
             return;
         }
     }
@@ -425,19 +336,9 @@ __global__ __launch_bounds__(kDirectThreads) void k_stream_g16(ScanArgs a, int64
     }
     if (kMode == 1) {
         uint64_t* part = reinterpret_cast<uint64_t*>(tail);
-        if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-        a.lane_counts[lane] = (uint32_t)L.count;
-        const uint64_t wsum = wave_sum(L.count);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = wsum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < kDirectThreads / kWave; ++w) t += part[w];
-            a.chunk_total[blockIdx.x] = t;
-        }
+        pass_count_epilogue<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, part, L.count, st);
     }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
 }
 
 // Count / emit passes over the fallback form of a large table (front.hpp, scan_block.hpp: fb_lane): the comb of entries
@@ -483,38 +384,16 @@ __global__ __launch_bounds__(kThreads, (kMode == 1 ? 8 : 2)) void k_stream_fb(Sc
     uint32_t st = 0;
     uint64_t base = 0;
     if (kMode == 2) {
-        uint32_t* wpart = reinterpret_cast<uint32_t*>(tail + 64 * group);
-        const uint32_t mine = live ? a.lane_counts[lane] : 0u;
-        const uint32_t incl = wave_scan_incl(mine);
-        if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[gtid / kWave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < gtid / kWave; ++w) wbase += wpart[w];
-        if (live) base = a.chunk_base[chunk] + wbase + incl - mine;
-        // (bases grow with the chunk index: if the last chunk of this workgroup does not fit, the output is void anyway)
-        const int64_t last = ((int64_t)blockIdx.x + 1) * kGroups - 1 < n_chunks - 1 ? ((int64_t)blockIdx.x + 1) * kGroups - 1 : n_chunks - 1;
-        if (a.chunk_base[last] + a.chunk_total[last] > a.cap) {
-            if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+        base = pass_emit_base<kDirectThreads>(a, chunk, gtid, live, reinterpret_cast<uint32_t*>(tail + 64 * group));
+        if (pass_over_capacity(a, pass_last_chunk<kGroups>(n_chunks))) {       // (uniform for the workgroup)
+            pass_publish(a.status, kStCapacity);
             return;
         }
     }
     // (a lane of a chunk beyond the workspace starts beyond the input: it is done before it begins)
     fb_lane<kMode>(a, T, live ? lane : (a.vend + lane_bytes - 1) / lane_bytes, lane_bytes, ring, base, L, st, kMode == 2 ? wsc : nullptr);
-    if (kMode == 1) {
-        uint64_t* part = reinterpret_cast<uint64_t*>(tail + 64 * group);
-        if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-        if (live) a.lane_counts[lane] = (uint32_t)L.count;
-        const uint64_t wsum = wave_sum(L.count);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[gtid / kWave] = wsum;
-        __syncthreads();
-        if (gtid == 0 && live) {
-            uint64_t t = 0;
-            for (int w = 0; w < kDirectThreads / kWave; ++w) t += part[w];
-            a.chunk_total[chunk] = t;
-        }
-    }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    if (kMode == 1) pass_count_epilogue<kDirectThreads>(a, chunk, gtid, live, reinterpret_cast<uint64_t*>(tail + 64 * group), L.count, st);
+    pass_publish(a.status, st);
 }
 // The copy form of a large table (scan_block.hpp: fb_lane<3> / fb_copy_lane).
 // Mark pass: the comb walk of k_stream_fb<1> plus the events; one 1024-lane workgroup per CU (the event stages take the
@@ -555,19 +434,8 @@ __global__ __launch_bounds__(kFbMarkThreads, 4) void k_fb_mark(ScanArgs a, FbCop
     uint32_t st = 0;
     // (a lane of a chunk beyond the workspace is not walked: it has no header and no events)
     if (live) fb_lane<3>(a, T, lane, lane_bytes, stage, 0, L, st, nullptr, &ca);
-    uint64_t* part = reinterpret_cast<uint64_t*>(tail + 64 * group);
-    if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-    if (live) a.lane_counts[lane] = (uint32_t)L.count;
-    const uint64_t wsum = wave_sum(live ? L.count : 0ull);
-    if ((threadIdx.x & (kWave - 1)) == 0) part[gtid / kWave] = wsum;
-    __syncthreads();
-    if (gtid == 0 && live) {
-        uint64_t t = 0;
-        for (int w = 0; w < kDirectThreads / kWave; ++w) t += part[w];
-        a.chunk_total[chunk] = t;
-    }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_count_epilogue<kDirectThreads>(a, chunk, gtid, live, reinterpret_cast<uint64_t*>(tail + 64 * group), L.count, st);
+    pass_publish(a.status, st);
 }
 // The same pass on the mark form of the comb (scan_block.hpp: fb_mark4_lane; front.hpp: fb_comb4): 32-bit entries.
 //   smem: 4 x cls[256] | comb4 | dense4 | literals' meta (u16) | event stages[1024 x 68] | 64 x groups
@@ -610,19 +478,8 @@ __global__ __launch_bounds__(kFbMarkThreads, 4) void k_fb_mark4(ScanArgs a, FbCo
     DirectLane L;
     uint32_t st = 0;
     if (live) fb_mark4_lane(a, T, lane, lane_bytes, stage, L, st, ca);
-    uint64_t* part = reinterpret_cast<uint64_t*>(tail + 64 * group);
-    if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-    if (live) a.lane_counts[lane] = (uint32_t)L.count;
-    const uint64_t wsum = wave_sum(live ? L.count : 0ull);
-    if ((threadIdx.x & (kWave - 1)) == 0) part[gtid / kWave] = wsum;
-    __syncthreads();
-    if (gtid == 0 && live) {
-        uint64_t t = 0;
-        for (int w = 0; w < kDirectThreads / kWave; ++w) t += part[w];
-        a.chunk_total[chunk] = t;
-    }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_count_epilogue<kDirectThreads>(a, chunk, gtid, live, reinterpret_cast<uint64_t*>(tail + 64 * group), L.count, st);
+    pass_publish(a.status, st);
 }
 // The second pass — no automaton — as a wave-cooperative splice (splice_block.hpp): a workgroup takes kThreads / 256 chunks of the workspace (256
 // sub-ranges of the mark pass each), the four waves of a chunk take its sub-ranges in turn, a whole wave on each.  The pass
@@ -646,18 +503,9 @@ __global__ __launch_bounds__(kThreads) void k_fb_splice(ScanArgs a, FbCopyArgs c
     const int64_t chunk = (int64_t)blockIdx.x * kGroups + group;
     const bool live = chunk < n_chunks;
     const int64_t lane0 = chunk * kDirectThreads;
-    uint32_t* wpart = wparts + 16 * group;
-    const uint32_t mine = live ? a.lane_counts[lane0 + gtid] : 0u;
-    const uint32_t incl = wave_scan_incl(mine);
-    if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[gtid / kWave] = incl;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < gtid / kWave; ++w) wbase += wpart[w];
-    sbase[threadIdx.x] = live ? a.chunk_base[chunk] + wbase + incl - mine : 0ull;
-    // (bases grow with the chunk index: if the last chunk of this workgroup does not fit, the output is void anyway)
-    const int64_t last = ((int64_t)blockIdx.x + 1) * kGroups - 1 < n_chunks - 1 ? ((int64_t)blockIdx.x + 1) * kGroups - 1 : n_chunks - 1;
-    if (a.chunk_base[last] + a.chunk_total[last] > a.cap) {               // (uniform for the workgroup)
-        if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+    sbase[threadIdx.x] = pass_emit_base<kDirectThreads>(a, chunk, gtid, live, wparts + 16 * group);
+    if (pass_over_capacity(a, pass_last_chunk<kGroups>(n_chunks))) {       // (uniform for the workgroup)
+        pass_publish(a.status, kStCapacity);
         return;
     }
     // a void launch (the mark pass met a NUL, or more events than a row holds): nothing is written, finish() runs the count / emit pair
@@ -687,15 +535,9 @@ __global__ __launch_bounds__(kGenThreads) void k_gen(ScanArgs a, GenArgs ga, int
     const GenView G = gen_view(a.blob);
     uint64_t base = 0;
     if (kMode == 2) {
-        const uint32_t mine = a.lane_counts[lane];
-        const uint32_t incl = wave_scan_incl(mine);
-        if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[threadIdx.x / kWave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < (int)threadIdx.x / kWave; ++w) wbase += wpart[w];
-        base = a.chunk_base[blockIdx.x] + wbase + incl - mine;
-        if (a.chunk_base[blockIdx.x] + a.chunk_total[blockIdx.x] > a.cap) {
-            if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+        base = pass_emit_base<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, wpart);
+        if (pass_over_capacity(a, blockIdx.x)) {               // (uniform for the workgroup)
+            pass_publish(a.status, kStCapacity);
             return;
         }
     }
@@ -703,19 +545,9 @@ __global__ __launch_bounds__(kGenThreads) void k_gen(ScanArgs a, GenArgs ga, int
     uint32_t st = 0;
     gen_lane<kMode>(a, G, ga, lane, lane_bytes, base, L, st);
     if (kMode == 1) {
-        if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-        a.lane_counts[lane] = (uint32_t)L.count;
-        const uint64_t wsum = wave_sum(L.count);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = wsum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < kGenThreads / kWave; ++w) t += part[w];
-            a.chunk_total[blockIdx.x] = t;
-        }
+        pass_count_epilogue<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, part, L.count, st);
     }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
 }
 
 // The backtracking fallback (gen_block.hpp: bt_lane): persistent workgroups, one chunk of 256 lanes per turn — a thread's
@@ -737,15 +569,8 @@ __global__ __launch_bounds__(kGenThreads) void k_bt(ScanArgs a, GenArgs ga, int6
         uint64_t base = 0;
         bool skip = false;
         if (kMode == 2) {
-            const uint32_t mine = a.lane_counts[lane];
-            const uint32_t incl = wave_scan_incl(mine);
-            __syncthreads();
-            if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[threadIdx.x / kWave] = incl;
-            __syncthreads();
-            uint32_t wbase = 0;
-            for (int w = 0; w < (int)threadIdx.x / kWave; ++w) wbase += wpart[w];
-            base = a.chunk_base[chunk] + wbase + incl - mine;
-            if (a.chunk_base[chunk] + a.chunk_total[chunk] > a.cap) { st |= kStCapacity; skip = true; }
+            base = pass_emit_base<kGenThreads, true>(a, chunk, threadIdx.x, true, wpart);
+            if (pass_over_capacity(a, chunk)) { st |= kStCapacity; skip = true; }
         }
         DirectLane L;
         uint32_t lst = 0;
@@ -754,22 +579,9 @@ __global__ __launch_bounds__(kGenThreads) void k_bt(ScanArgs a, GenArgs ga, int6
         if (lst & kStEditOverflow) { atomicOr(a.status + 2, why); atomicOr(a.status, kStEditOverflow); }      // (status[2]: which limit, for the runtime's next try)
         if (kMode == 1 && (lst & kStDiverge)) atomicMax(a.status + 1, 0xffffffffu - (uint32_t)lane);     // (see k_stream_direct)
         st |= lst;
-        if (kMode == 1) {
-            if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-            a.lane_counts[lane] = (uint32_t)L.count;
-            const uint64_t wsum = wave_sum(L.count);
-            __syncthreads();
-            if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = wsum;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint64_t t = 0;
-                for (int w = 0; w < kGenThreads / kWave; ++w) t += part[w];
-                a.chunk_total[chunk] = t;
-            }
-        }
+        if (kMode == 1) pass_count_epilogue<kGenThreads, true>(a, chunk, threadIdx.x, true, part, L.count, st);
     }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
 }
 
 // The deterministic engine on tables still being built (lazy_block.hpp): a thread per sub-range; a lane with a result from an
@@ -794,15 +606,9 @@ __global__ __launch_bounds__(kGenThreads) void k_lazy(ScanArgs a, LazyArgs la, i
     if (kMode == 2) {
         // the count pass met an unexplored edge (or gave up): its sizes are not final, nothing is written — finish() runs the next round
         if (*a.status & (kStMiss | kStEditOverflow | kStDiverge)) return;
-        const uint32_t mine = a.lane_counts[lane];
-        const uint32_t incl = wave_scan_incl(mine);
-        if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[threadIdx.x / kWave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < (int)threadIdx.x / kWave; ++w) wbase += wpart[w];
-        base = a.chunk_base[blockIdx.x] + wbase + incl - mine;
-        if (a.chunk_base[blockIdx.x] + a.chunk_total[blockIdx.x] > a.cap) {
-            if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+        base = pass_emit_base<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, wpart);
+        if (pass_over_capacity(a, blockIdx.x)) {               // (uniform for the workgroup)
+            pass_publish(a.status, kStCapacity);
             return;
         }
     }
@@ -815,23 +621,15 @@ __global__ __launch_bounds__(kGenThreads) void k_lazy(ScanArgs a, LazyArgs la, i
             L.count = have;
         } else {
             lazy_lane<1>(a, la, lane, lane_bytes, 0, L, st, voided);
-            if (L.count >= kLazyVoid) { st |= kStCapacity; L.count = kLazyVoid - 1u; }
+            pass_saturate(L.count, st, kLazyVoid - 1u);
             a.lane_counts[lane] = voided || (st & (kStEditOverflow | kStDiverge)) ? kLazyVoid : (uint32_t)L.count;
             if (voided) L.count = 0;
         }
-        const uint64_t wsum = wave_sum(L.count);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = wsum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < kGenThreads / kWave; ++w) t += part[w];
-            a.chunk_total[blockIdx.x] = t;
-        }
+        pass_count_reduce<kGenThreads>(a, blockIdx.x, threadIdx.x, true, part, L.count);
     } else {
         lazy_lane<2>(a, la, lane, lane_bytes, base, L, st, voided, a.lane_counts[lane]);
     }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
 }
 
 // Exact sub-ranges (scan_block.hpp: ScanArgs::exact): lane i's entry state must be the exit state of lane i - 1 — an entry that was
@@ -1140,14 +938,6 @@ void launch_g16(int which, const ScanArgs& a, int64_t lane_bytes, int64_t n_bloc
 // Workgroups are persistent: each takes tiles (kOneThreads lanes of oa.lane_bytes bytes) from a ticket counter until none is left.
 //   smem: cls[256] | g16[g16_room] | pooled text (2 KiB) | regions[kOneThreads x R] + 32 | offs[kOneThreads + 4] | exits[kOneThreads] |
 //         misc[16] | marks[kOneThreads x R / 16 + 16]
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    const int lid = threadIdx.x & (kWave - 1);
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, kWave);
-        if (lid >= d) v += o;
-    }
-    return v;
-}
 // the tile's tail: sizes, look-back, stores (a function of its own: its registers are not the walk's)
 // (everything by value: a reference to the kernel's arguments would put a copy of them on the stack — scratch memory per lane, and the
 // scratch ring's size is what the dispatcher admits waves by)
@@ -1171,7 +961,7 @@ __device__ __forceinline__ uint32_t one_tail(OneTailArgs q, const uint8_t* regio
     struct { uint64_t *desc, *gsum, *ginc, *total; int64_t n_tiles; uint32_t spin; } oa{q.desc, q.gsum, q.ginc, q.total, q.n_tiles, q.spin};
         // ---- sizes: the lanes' places in the tile's output ---------------------------------------------------------------------------
         const uint32_t len = tile_void ? 0u : count;
-        const uint32_t incl = wave_incl_scan_u32(len);
+        const uint32_t incl = wave_scan_incl(len);
         if (lid == kWave - 1) misc[wave] = incl;
         __syncthreads();
         uint32_t woff = 0;
@@ -1532,34 +1322,18 @@ __global__ __launch_bounds__(kDirectThreads) void k_wide_fwd(ScanArgs a, int64_t
     uint32_t st = 0;
     uint64_t base = 0;
     if (kMode == 2) {
-        const uint32_t mine = a.lane_counts[lane];
-        const uint32_t incl = wave_scan_incl(mine);
-        if ((threadIdx.x & (kWave - 1)) == kWave - 1) wpart[threadIdx.x / kWave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int w = 0; w < (int)threadIdx.x / kWave; ++w) wbase += wpart[w];
-        base = a.chunk_base[blockIdx.x] + wbase + incl - mine;
-        if (a.chunk_base[blockIdx.x] + a.chunk_total[blockIdx.x] > a.cap) {
-            if (threadIdx.x == 0) atomicOr(a.status, kStCapacity);
+        base = pass_emit_base<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, wpart);
+        if (pass_over_capacity(a, blockIdx.x)) {               // (uniform for the workgroup)
+            pass_publish(a.status, kStCapacity);
             return;
         }
     }
     wide_fwd_lane<kMode>(a, T, h.n_cls, lane, lane_bytes, base, L, st);
     if (kMode == 1 && (st & kStDiverge)) atomicMax(a.status + 1, 0xffffffffu - (uint32_t)lane);     // (see k_stream_direct)
     if (kMode == 1) {
-        if (L.count > 0xffffffffull) { st |= kStCapacity; L.count = 0xffffffffull; }
-        a.lane_counts[lane] = (uint32_t)L.count;
-        const uint64_t wsum = wave_sum(L.count);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = wsum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < kDirectThreads / kWave; ++w) t += part[w];
-            a.chunk_total[blockIdx.x] = t;
-        }
+        pass_count_epilogue<kDirectThreads>(a, blockIdx.x, threadIdx.x, true, part, L.count, st);
     }
-    st = wave_or(st);
-    if (st && (threadIdx.x & (kWave - 1)) == 0) atomicOr(a.status, st);
+    pass_publish(a.status, st);
 }
 void launch_rev_wide(const ScanArgs& a, int64_t lane_bytes, void* stream) {
     const int64_t vtop = (a.vend + 63) & ~(int64_t)63;
@@ -1572,21 +1346,23 @@ void launch_wide_fwd(int which, const ScanArgs& a, int64_t lane_bytes, int64_t n
     else hipLaunchKernelGGL((k_wide_fwd<2>), dim3((unsigned)n_blocks), dim3(kDirectThreads), 0, s, a, lane_bytes);
 }
 
+// LDS of the mark pass (the carves of k_fb_mark / k_fb_mark4): cls | comb (mark4: comb4 | dense4) | literals' meta | event stages | 64 per chunk
+int fb_mark_lds(const StreamBlobHeader& h, bool mark4) {
+    const int comb = mark4 ? (int)((h.fb4_slots * 4u + 15u) & ~15u) + (int)h.fb4_dense * 128 : (int)((h.fb_slots * 8u + 15u) & ~15u);
+    return 256 + comb + (int)((h.fb_lits * 2u + 15u) & ~15u) + kFbMarkThreads * kMarkStageStride * 4 + 64 * (kFbMarkThreads / kDirectThreads);
+}
 void launch_fb_mark(const ScanArgs& a, const FbCopyArgs& ca, const void* hdr, int64_t lane_bytes, int64_t n_chunks, void* stream) {
     const StreamBlobHeader& h = *static_cast<const StreamBlobHeader*>(hdr);
     constexpr int kG = kFbMarkThreads / kDirectThreads;
     // the mark form of the comb where the tables have it (TRRE_NO_FB_MARK4=1: the 8-byte comb, for A/B runs)
     const bool no_mark4 = switches().no_fb_mark4;
     if (h.fb4_slots && !no_mark4) {
-        const int lds4 = 256 + (int)((h.fb4_slots * 4u + 15u) & ~15u) + (int)h.fb4_dense * 128 + (int)((h.fb_lits * 2u + 15u) & ~15u) +
-                         kFbMarkThreads * kMarkStageStride * 4 + 64 * kG;
         allow_big_lds<&k_fb_mark4>();
-        hipLaunchKernelGGL(k_fb_mark4, dim3((unsigned)((n_chunks + kG - 1) / kG)), dim3(kFbMarkThreads), lds4, static_cast<hipStream_t>(stream), a, ca, lane_bytes, n_chunks);
+        hipLaunchKernelGGL(k_fb_mark4, dim3((unsigned)((n_chunks + kG - 1) / kG)), dim3(kFbMarkThreads), fb_mark_lds(h, true), static_cast<hipStream_t>(stream), a, ca, lane_bytes, n_chunks);
         return;
     }
-    const int lds = 256 + (int)((h.fb_slots * 8u + 15u) & ~15u) + (int)((h.fb_lits * 2u + 15u) & ~15u) + kFbMarkThreads * kMarkStageStride * 4 + 64 * kG;
     allow_big_lds<&k_fb_mark>();
-    hipLaunchKernelGGL(k_fb_mark, dim3((unsigned)((n_chunks + kG - 1) / kG)), dim3(kFbMarkThreads), lds, static_cast<hipStream_t>(stream), a, ca, lane_bytes, n_chunks);
+    hipLaunchKernelGGL(k_fb_mark, dim3((unsigned)((n_chunks + kG - 1) / kG)), dim3(kFbMarkThreads), fb_mark_lds(h, false), static_cast<hipStream_t>(stream), a, ca, lane_bytes, n_chunks);
 }
 // workgroup size of the copy pass: the largest whose rings fit next to the literals
 int fb_splice_lds(const StreamBlobHeader& h, int threads, bool lit_lds) {
@@ -1647,8 +1423,7 @@ void launch_bt(int which, const ScanArgs& a, const GenArgs& ga, int64_t lane_byt
 bool fb_copy_fits(const void* hdr) {
     const StreamBlobHeader& h = *static_cast<const StreamBlobHeader*>(hdr);
     if (!h.off_fb_lit_meta) return false;
-    const int mark = 256 + (int)((h.fb_slots * 8u + 15u) & ~15u) + (int)((h.fb_lits * 2u + 15u) & ~15u) + kFbMarkThreads * kMarkStageStride * 4 + 256;
-    return mark <= kLdsLimit;
+    return fb_mark_lds(h, false) <= kLdsLimit;
 }
 
 constexpr int kFbCountThreads = 1024, kFbEmitThreads = 512;
@@ -1672,7 +1447,7 @@ void launch_fb_kernel(int which, const ScanArgs& a, const void* hdr, int64_t lan
     }
 }
 // the fallback form fits next to the emit pass's rings
-bool fb_fits(const void* hdr) { return fb_lds_bytes(*static_cast<const StreamBlobHeader*>(hdr), 2) <= 160 * 1024; }
+bool fb_fits(const void* hdr) { return fb_lds_bytes(*static_cast<const StreamBlobHeader*>(hdr), 2) <= kLdsLimit; }
 
 void launch_chunk_scan(const uint64_t* total, uint64_t* base, int64_t n_chunks, void* stream) {
     hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), total, base, n_chunks);
