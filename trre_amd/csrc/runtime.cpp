@@ -2063,6 +2063,7 @@ int generate_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, std:
         // sum, emit.  A chunk on which a path never returns, a search goes deeper than a lane's stack or the sizes leave 32 bits
         // goes to the host enumeration below, which also knows what the reference had printed when it gave up.
         bool done = false;
+        uint32_t handed_over = 0;                                           // the status bits that sent the chunk to the host
         if (!switches().gen_host) {
             const int64_t n_lanes_raw = ((int64_t)len + kGenLaneBytes - 1) / kGenLaneBytes;
             const int64_t n_chunks = (n_lanes_raw + 255) / 256, n_lanes = n_chunks * 256;
@@ -2086,7 +2087,8 @@ int generate_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, std:
             HIP_TRY(hipMemcpyAsync(hs.ctx.h_status, hs.ctx.d_status, 8, hipMemcpyDeviceToHost, hs.stream));
             HIP_TRY(hipMemcpyAsync(&total, hs.ctx.d_chunk_base + n_chunks, 8, hipMemcpyDeviceToHost, hs.stream));
             HIP_TRY(hipStreamSynchronize(hs.stream));
-            if (!(hs.ctx.h_status[0] & (kStDiverge | kStEditOverflow | kStCapacity))) {
+            handed_over = hs.ctx.h_status[0] & (kStDiverge | kStEditOverflow | kStCapacity);
+            if (!handed_over) {
                 // (the symbols sit in the slot's output buffer: the output gets a buffer of its own, kept by the context)
                 const size_t want = (size_t)total + (size_t)total / 4 + 4096;          // (head room: grown only when total + 64 does not fit)
                 if (hs.ctx.d_gen_out.cap < total + 64 && hs.ctx.d_gen_out.reserve(want, want) != hipSuccess)
@@ -2105,6 +2107,12 @@ int generate_on(trre_prog* p, DeviceState* st, const uint8_t* in, size_t n, std:
                 HIP_TRY(hipStreamSynchronize(hs.stream));
                 done = true;
             }
+        }
+        // (TRRE_TRACE: who enumerated this chunk — the tests read it: the host enumeration is the fallback AND the checker)
+        if (switches().trace) {
+            if (done) fprintf(stderr, "trre: generate: chunk at %zu, %zu bytes: device\n", off, len);
+            else if (switches().gen_host) fprintf(stderr, "trre: generate: chunk at %zu, %zu bytes: host (TRRE_GEN_HOST)\n", off, len);
+            else fprintf(stderr, "trre: generate: chunk at %zu, %zu bytes: host (status 0x%x)\n", off, len, handed_over);
         }
         if (!done) {
             HIP_TRY(hipMemcpyAsync(hs.pin_out, hs.d_out, len, hipMemcpyDeviceToHost, hs.stream));

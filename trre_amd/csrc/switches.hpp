@@ -19,7 +19,7 @@ inline SwitchNum switch_narrow(const char* v) { return v ? SwitchNum{true, atoi(
 
 // read once per process
 struct Switches {
-    bool trace = switch_on(getenv("TRRE_TRACE"));                      // what the compile, the lazy rounds, the repair rounds, a void launch and the host path's stages did, on stderr
+    bool trace = switch_on(getenv("TRRE_TRACE"));                      // what the compile, the lazy rounds, the repair rounds, a void launch, the host path's stages and generator mode (who enumerated each chunk: the device or the host) did, on stderr
     bool no_stack_guard = switch_on(getenv("TRRE_NO_STACK_GUARD"));    // the stack guard (guard_block.hpp) off
     SwitchNum guard_budget = switch_wide(getenv("TRRE_GUARD_BUDGET")); // search steps per line of the stack guard; beyond: not decided
     SwitchNum guard_call_budget = switch_wide(getenv("TRRE_GUARD_CALL_BUDGET"));   // ... and per scan call, summed over its suspect lines
