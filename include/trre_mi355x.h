@@ -139,7 +139,7 @@ int trre_set_kernel(trre_prog* p, int kernel_family); /* force a family (benchma
  * tests).  Returns the blob size; copies min(size, cap) bytes. */
 size_t trre_export_tables(const trre_prog* p, void* buf, size_t cap);
 size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap); /* 0 if the pattern does not fold */
-size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables; 0 if none */
+size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted; 0 if none */
 
 /* Replaces the scan branch of main() (trre_nft.c:775-790 / trre_dft.c:1272-1286)
  * for a whole buffer that is already resident in HBM.
@@ -207,6 +207,40 @@ int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const 
  * `stream`. */
 int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
                              size_t cap, int64_t* d_out_off, size_t* out_len, void* stream);
+
+/* Matched strings: the same column of strings under a program compiled with TRRE_MODE_MATCH — which of the strings does the
+ * pattern accept, and what do the accepted ones become.  With M what the reference prints under `trre -m`, for string i
+ *     m_i = M(rec_i + "\n"),   valid[i] = (m_i is not empty),   out_i = m_i without its last byte (the framing '\n'),
+ * and out_i is empty when the string is rejected.  The outputs are concatenated into d_out; d_out_off[i] is where out_i
+ * starts, d_out_off[nrec] = *out_len; a rejected string has d_out_off[i + 1] == d_out_off[i].  A NUL cuts its line.  An empty
+ * string is an empty line: '(a:x)*' accepts it with an empty output, 'a+:x' rejects it, ':x' accepts it with "x".
+ * d_valid is an Arrow validity bitmap — bit i & 7 of byte i >> 3 — of 8 * ceil(nrec / 64) bytes, 8-byte aligned (anything else:
+ * TRRE_E_ARG), written as whole 64-bit words; the bits at and beyond nrec are zero.  *n_matched (may be null) receives the
+ * number of set bits.
+ * Arguments, overlaps (d_valid is one more array that overlaps nothing), d_in == d_out, d_out null with cap == 0, the offsets'
+ * check (TRRE_E_ARG, nothing written) and a split-form scan in flight: as for trre_scan_device_strings.
+ * Refused before the device is touched: a program not compiled with TRRE_MODE_MATCH (TRRE_E_ARG); one that can print a '\n' of
+ * its own (TRRE_E_UNSUPPORTED); one without guided tables — a backward automaton beyond 16 384 states, which runs on the
+ * backtracking family — or with TRRE_KERNEL_BACKTRACK forced through trre_set_kernel (TRRE_E_UNSUPPORTED: the verdicts come
+ * from the guided tables).  The scan itself always runs on the general guided family.
+ * A string that holds a '\n' would be several lines with several verdicts: TRRE_E_ARG, found on the device from the staged
+ * text's newline count before anything is written to d_out; d_out_off and d_valid are unspecified then.
+ *   TRRE_E_CAPACITY  exactly when the framed length minus n_matched exceeds cap; *out_len is that size.  d_out has not been
+ *                    written at all (in place the input is intact), d_out_off is unspecified, d_valid and *n_matched are
+ *                    valid: cap == 0 with d_out == NULL answers "which strings match, and how much room do their outputs
+ *                    need", and a retry with room works.
+ *   TRRE_E_DIVERGES  *out_len = 0; d_out, d_out_off and d_valid are unspecified; trre_last_error() holds the reference's
+ *                    message (a search that does not return, or one that exhausts the reference's stack).
+ * How: the strings call's staged text is scanned in match mode into the library's framed buffer; a line's fate is what the
+ * backward pass's symbol at its first byte says (one table lookup per string: the bitmap and the ranks M_i = accepted strings
+ * among 0 .. i); string i's framed output ends just past framed newline number M_i, and the framed output goes into d_out with
+ * every '\n' dropped.
+ * Device memory, kept by the (prog, device) until trre_free: the strings call's buffers — the staged text, n + nrec + 64
+ * bytes; the framed output, cap + nrec + 64 bytes; 24 bytes per 16 KiB of staged text and of framed output — plus the
+ * symbols of the staged text (1 byte per staged byte; half a byte up to 16 backward states, 2 bytes beyond 256) and the verdict
+ * workspace, 16 bytes per 256 strings.  Synchronous with respect to `stream`; trre_last_scan_flags as for the strings call. */
+int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
+                              size_t cap, int64_t* d_out_off, uint8_t* d_valid, size_t* n_matched, size_t* out_len, void* stream);
 
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */

@@ -94,6 +94,7 @@ def lib():
         L.trre_scan_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
         L.trre_scan_device_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_scan_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
+        L.trre_match_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -167,6 +168,14 @@ class Program:
             lib().trre_export_guided_tables(self._h, which, buf, n)
             blobs.append(buf.raw[:n])
         return tuple(blobs)
+
+    def export_accept_table(self):
+        """match mode, guided tables: one byte per backward state, 1 where a line whose first byte carries that symbol is
+        accepted (the verdict table of match_strings), or b"" """
+        n = lib().trre_export_guided_tables(self._h, 4, None, 0)
+        buf = ctypes.create_string_buffer(max(n, 1))
+        lib().trre_export_guided_tables(self._h, 4, buf, n)
+        return buf.raw[:n]
 
     def export_gen_tables(self):
         """generator modes: the tables of the device enumeration (gen_block.hpp), or b"" """
@@ -292,6 +301,56 @@ class Program:
     def scan_list(self, records, device=0):
         """list of bytes in -> list of bytes out, each record scanned as a file of its own (through scan_records)"""
         return self._map_list(records, device, self.scan_records)
+
+    def match_strings(self, values, offsets, out=None, out_offsets=None, stream=None, packed=False):
+        """Matched strings (trre_match_device_strings; a program compiled with mode="match"): values and offsets as for
+        scan_strings, no string holding a b"\\n".  Returns (out_values, out_offsets, valid): valid[i] says whether the pattern
+        accepts string i as a whole line, out_values[out_offsets[i]:out_offsets[i+1]] is what it becomes (empty when rejected).
+        valid is a torch.bool tensor of nrec entries; with packed=True it is the Arrow validity bitmap as the library wrote it
+        (uint8, 8 * ceil(nrec / 64) bytes, bit i & 7 of byte i >> 3).  out may be values itself; a too small out is replaced."""
+        import torch
+        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
+        n, nrec = values.numel(), offsets.numel() - 1
+        if out is None:
+            out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
+        if out_offsets is None:
+            out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        words = torch.zeros(max((nrec + 63) // 64, 1), dtype=torch.int64, device=values.device)     # (8-byte aligned)
+        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
+        m, k = ctypes.c_size_t(), ctypes.c_size_t()
+
+        def call(o):
+            return lib().trre_match_device_strings(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o.data_ptr(), o.numel(),
+                                                   out_offsets.data_ptr(), words.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
+        with torch.cuda.device(values.device):
+            rc = call(out)
+            if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
+                out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
+                rc = call(out)
+        _check(rc)
+        bitmap = words.view(torch.uint8)[:8 * ((nrec + 63) // 64)]
+        if packed:
+            return out[:m.value], out_offsets, bitmap
+        shifts = torch.arange(8, dtype=torch.uint8, device=values.device)
+        valid = ((bitmap.unsqueeze(1) >> shifts) & 1).to(torch.bool).flatten()[:nrec]
+        return out[:m.value], out_offsets, valid
+
+    def match_list(self, records, device=0):
+        """list of bytes in -> list out: what an accepted string becomes (bytes), None for a rejected one (through match_strings)"""
+        import numpy as np
+        import torch
+        recs = [_bytes(r) for r in records]
+        off = np.zeros(len(recs) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in recs], out=off[1:])
+        dev = torch.device("cuda", device)
+        packed = b"".join(recs)
+        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
+        out, out_off, valid = self.match_strings(values, torch.from_numpy(off).to(dev))
+        blob = out.cpu().numpy().tobytes()
+        o = out_off.cpu().numpy().tolist()
+        ok = valid.cpu().numpy().tolist()
+        return [blob[o[i]:o[i + 1]] if ok[i] else None for i in range(len(recs))]
 
     @staticmethod
     def _map_list(records, device, scan):

@@ -397,6 +397,9 @@ struct GuidedTables {
     std::vector<uint8_t> rev;               // [n_rev][n_cls] next state (n_rev <= 256)
     std::vector<uint16_t> rev16;            // the same when wide
     StreamTables fwd;                       // columns = symbols (fwd.cls is unused)
+    std::vector<uint8_t> accept;            // match mode: [n_rev] 1 where the forward root cell at that symbol takes a follow entry, i.e. a
+                                            // line whose first byte (its '\n' when it is empty) carries the symbol is accepted
+                                            // (trre_match_device_strings: the verdicts)
 };
 // With nodes built for match mode the tables compute `trre -m` (trre_nft.c:791-797): one attempt per line from its first
 // byte, accepted only if it ends exactly at the end of the line; an accepted line prints its output and '\n', a

@@ -91,6 +91,7 @@ public:
         byte_classes(g);
         backward(g);
         forward(g);
+        if (match_) fill_accept(g);
         g.wide = g.n_rev > 256;
         g.sym_bits = g.wide ? 16 : ((g.n_rev <= 16 && g.fwd.g16_ok) ? 4 : 8);
         g.ok = true;
@@ -98,6 +99,15 @@ public:
     }
 
 private:
+    // match mode: which symbols at a line's first byte mean "accepted" — the root cell's own question (match_cell, s == 0): does
+    // the start list hold an entry the search does not get past.  (An entry that diverges counts: such a line never reaches the
+    // verdicts, its scan has failed by then.)
+    void fill_accept(GuidedTables& g) const {
+        g.accept.assign(g.n_rev, 0);
+        for (uint32_t y = 0; y < g.n_rev; ++y)
+            g.accept[y] = decisive(nd_.follow[n_nodes_], rev_[y], y == kSymEol || y == kSymNul) >= 0 ? 1 : 0;
+    }
+
     // bytes read by the same nodes behave alike; '\n' and NUL never occur inside a line
     void byte_classes(GuidedTables& g) {
         std::map<std::vector<uint32_t>, uint8_t> index;

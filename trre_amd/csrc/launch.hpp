@@ -13,6 +13,7 @@ struct OneArgs;
 struct MapGenArgs;
 struct RecArgs;
 struct StrArgs;
+struct MatchArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -95,6 +96,14 @@ void launch_str_part(int side, const StrArgs& a, int64_t* part, int64_t tiles, v
 void launch_str_stage(const StrArgs& a, int64_t tiles, void* stream);
 void launch_str_rank(const StrArgs& a, void* stream);
 void launch_str_unframe(const StrArgs& a, int64_t tiles, void* stream);
+// matched strings (records_block.hpp): the verdicts (sym_bits: 4, 8 or 16, the layout of the symbols), their bitmap, the local ranks and the
+// groups' counts; the ranks; the final offsets; '\n' per tile of the compaction (the strings' tiles); the compaction that drops every '\n'
+// (a.part: the '\n' before every tile)
+void launch_match_verdict(int sym_bits, const MatchArgs& a, void* stream);
+void launch_match_rank(const MatchArgs& a, void* stream);
+void launch_match_final(const MatchArgs& a, void* stream);
+void launch_match_count(const RecArgs& a, int64_t tiles, void* stream);
+void launch_match_unframe(const StrArgs& a, int64_t tiles, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

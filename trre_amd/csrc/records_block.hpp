@@ -513,4 +513,85 @@ TRRE_HD void str_unframe_vecs(const StrArgs& a, const StrTile<G>& t, const StrOu
     }
 }
 
+// ---- matched strings (trre_match_device_strings) ---------------------------------------------------------------------------
+// A match-mode program accepts a string or rejects it: valid[i], and out_i = M(rec_i + '\n') minus the framing '\n' (empty when
+// rejected).  The staged text is the strings call's; no string holds a '\n' (the staged newline total is nrec exactly then) and
+// the program prints none of its own, so every '\n' of the framed output closes exactly one ACCEPTED string, in order.  With
+//     M_i = number of accepted strings among 0 .. i
+// string i's framed output ends just past framed newline number M_i (position 0 when M_i is 0), its final offset is that
+// position minus M_i, and the output bytes are the framed output with every '\n' dropped.  Whether string i is accepted is what
+// the forward root cell decides at the column of the backward pass's symbol at the string's first staged byte,
+// s_i = off[i] + i (its '\n' when the string is empty): accept[symbol] (guided_build.cpp: fill_accept).  The passes:
+//   k_rec_check, k_str_part(0), k_str_stage, k_chunk_scan   as for the strings call; the staged newline total
+//   (the plain match scan of the staged text into the framed buffer; a guided family: the symbols are in the context)
+//   k_match_verdict   64 strings per wave: the bitmap word (one ballot), the rank inside the group of THREADS strings in
+//                     out_off[i + 1], the group's count
+//   k_chunk_scan, k_match_rank   M_i = group base + local rank, in out_off[i + 1]; the grand total is n_matched
+//   k_rec_count, k_chunk_scan, k_rec_part(1), k_rec_locate   out_off[i + 1] = position just past framed newline M_i (as above)
+//   k_match_final     out_off[i + 1] -= M_i, M_i again from the group bases and the bitmap words
+//   k_match_count, k_chunk_scan   '\n' per framed tile of the compaction and before it
+//   k_match_unframe   k_str_unframe's compaction with the marks taken from the bytes: every '\n' goes
+constexpr int kMatchThreads = 256;                    // strings per group: four bitmap words
+
+struct MatchArgs {
+    const uint8_t* sym_v0;    // the backward pass's symbols of the staged text, in the scan's v-space
+    int64_t vbeg;             // the staged text's address mod 16
+    const int64_t* off;       // [nrec + 1] the caller's offsets
+    int64_t nrec;
+    const uint32_t* accept;   // a bit per backward state
+    uint32_t accept_words;
+    uint64_t* valid;          // [words] the bitmap
+    int64_t words;            // ceil(nrec / 64)
+    int64_t* out_off;         // [nrec + 1] local ranks, M_i, located positions, then the output offsets
+    uint64_t* cnt;            // [groups] accepted strings per group
+    const uint64_t* base;     // [groups + 1] exclusive scan of cnt
+};
+
+// the symbol at v: kBits 4 two per byte, 8 one per byte (rev_symbol_at), 16 two bytes each
+template <int kBits>
+TRRE_HD uint32_t match_symbol_at(const uint8_t* sym_v0, int64_t v) {
+    if (kBits == 16) return reinterpret_cast<const uint16_t*>(sym_v0)[v];
+    ScanArgs s{};
+    s.sym_v0 = const_cast<uint8_t*>(sym_v0);
+    return rev_symbol_at<kBits == 4>(s, v);
+}
+// k_match_verdict, one lane: is string i accepted (acc: the accept bits, in LDS on the device)
+template <int kBits>
+TRRE_HD bool match_verdict(const MatchArgs& a, const uint32_t* acc, int64_t i) {
+    const uint32_t y = match_symbol_at<kBits>(a.sym_v0, a.off[i] + i + a.vbeg);
+    return y < 32u * a.accept_words && ((acc[y >> 5] >> (y & 31u)) & 1u) != 0;
+}
+TRRE_HD uint32_t match_popc64(uint64_t x) { return (uint32_t)__builtin_popcountll(x); }
+// ... the lane's inclusive rank inside its wave's word
+TRRE_HD uint32_t match_lane_rank(uint64_t word, int lane) { return match_popc64(word & (~0ull >> (63 - lane))); }
+// ... what the group's lane `tid` leaves: its rank in the group (below: the accepted strings of the waves before its own)
+TRRE_HD void match_park(const MatchArgs& a, int64_t i, uint32_t below, uint64_t word, int lane) {
+    if (i < a.nrec) a.out_off[i + 1] = (int64_t)(below + match_lane_rank(word, lane));
+}
+// k_match_rank: the group's base onto string i's local rank
+TRRE_HD void match_add_base(const MatchArgs& a, int64_t i) {
+    a.out_off[i + 1] = (int64_t)((uint64_t)a.out_off[i + 1] + a.base[i / kMatchThreads]);
+}
+// M_i from the group bases and the bitmap words
+TRRE_HD uint64_t match_rank_of(const MatchArgs& a, int64_t i) {
+    const int64_t w = i >> 6;
+    uint64_t r = a.base[i / kMatchThreads];
+    for (int64_t k = (i / kMatchThreads) * (kMatchThreads / 64); k < w; ++k) r += match_popc64(a.valid[k]);
+    return r + match_lane_rank(a.valid[w], (int)(i & 63));
+}
+// k_match_final: the located position minus the framing newlines before it
+TRRE_HD void match_final(const MatchArgs& a, int64_t i) {
+    a.out_off[i + 1] = (int64_t)((uint64_t)a.out_off[i + 1] - match_rank_of(a, i));
+}
+// k_match_unframe: the marks of the thread's vectors from their bytes — every '\n' of the framed tile (vector k of the image is
+// vector k of the tile: the compaction's source has no shift)
+template <class G>
+TRRE_HD void match_mark_vecs(const StrTile<G>& t, int tid, const U128 (&w)[G::VECS + 1], uint16_t* bits16) {
+    for (int j = 0; j < G::VECS; ++j) {
+        const int q = j * G::THREADS + tid;
+        const int64_t v = t.v0 + 16 * (int64_t)q;
+        bits16[q] = v < t.vend ? (uint16_t)(rec_nl16(w[j]) & rec_valid16(v, 0, t.vend)) : (uint16_t)0;
+    }
+}
+
 }  // namespace trre

@@ -169,6 +169,7 @@ struct ScanCtx {
     DevBuf<uint64_t> d_rec;           // trre_scan_device_records: status word, then part [tiles + 1], cnt [tiles], base [tiles + 1] (tiles)
     DevBuf<uint8_t> d_gen_out;        // generator modes: the enumeration's output before it goes down (bytes)
     DevBuf<uint8_t> d_framed;         // trre_scan_device_strings: the scan's output with every record's closing '\n' still in it (bytes)
+    DevBuf<uint64_t> d_match;         // trre_match_device_strings: accepted strings per group of 256, then their exclusive scan [groups + 1] (groups)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
     DevBuf<uint32_t> d_cevents, d_chdr;
@@ -209,6 +210,7 @@ struct DeviceState {
     uint8_t* d_rblob = nullptr;       // ... and the backward DFA
     uint8_t* d_nblob = nullptr;       // generator modes: the enumeration's tables
     uint8_t* d_kblob = nullptr;       // the stack guard's tables (the NFT itself)
+    uint8_t* d_ablob = nullptr;       // match mode: a bit per backward state, set where a line that starts with that symbol is accepted
     // the deterministic engine's tables while they are being built (front.hpp: LazyDft): this device's copy and how much of the host's it holds.
     // A buffer that has to grow is replaced, not freed: scans of other chunks may still be reading it (freed with the state).
     uint64_t* d_lent = nullptr;
@@ -260,6 +262,7 @@ struct trre_prog {
     std::mutex lazy_mu;               // explore() and the uploads
     trre::GuardTables guard;          // scan mode, NFT engine: which lines can exhaust the reference's stack (stack_guard.cpp)
     std::vector<uint8_t> kblob;
+    std::vector<uint8_t> ablob;       // match mode, guided tables: GuidedTables::accept as bits (32-bit words; trre_match_device_strings)
     int mask_bytes = 0;
     bool profiling = false;
     std::atomic<float> last_ms{-1.f};
@@ -499,6 +502,8 @@ bool is_gen(int fam) {
     return fam == TRRE_KERNEL_TILE_GEN || fam == TRRE_KERNEL_STREAM_GEN || fam == TRRE_KERNEL_GUIDED_GEN || fam == TRRE_KERNEL_BACKTRACK || fam == TRRE_KERNEL_DFT_LAZY;
 }
 bool is_guided_wide(const trre_prog& p, int fam) { return (fam == TRRE_KERNEL_GUIDED_LP || fam == TRRE_KERNEL_GUIDED_GEN) && p.gt.wide; }
+// how the guided families' backward pass stores its symbols: 4 two per byte, 8 one per byte, 16 two bytes each (wide tables)
+int guided_sym_bits(const trre_prog& p) { return p.gt.wide ? 16 : (p.gt.sym_bits == 4 && !trre::switches().no_g16 ? 4 : 8); }
 bool lp_inplace(uint32_t flags) { return (flags & trre::kFlagLengthPreserving) && (flags & trre::kFlagNoOverrun); }
 // the family that takes over when a length-preserving launch met a NUL, or a bounded stream table a long run
 int general_family(const trre_prog& p, bool stream_ok) {
@@ -607,6 +612,7 @@ int device_state(trre_prog* p, int dev, DeviceState** out) {
         if (!rc) rc = upload(p->rblob, &st->d_rblob);
         if (!rc) rc = upload(p->nblob, &st->d_nblob);
         if (!rc) rc = upload(p->kblob, &st->d_kblob);
+        if (!rc) rc = upload(p->ablob, &st->d_ablob);
         if (!rc) rc = ctx_init(st->ctx);
         if (rc) return rc;
         if (trace_on) fprintf(stderr, "trre: device %d: tables up in %.1f ms\n", dev, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -987,7 +993,7 @@ LaunchPlan make_plan(const trre_prog* p, const DeviceState* st, const ScanCtx* c
     // A program whose longer texts turn out to be frequent (finish(): the output 4 % longer than the input; `a:xyz` on text: 8.6 ms against 8.0)
     // goes back to the pair for the context's later scans.  TRRE_MAPGEN=1: every memoryless program, always; TRRE_MAPGEN=0: none
     pl.mapgen_on = stt.mg_max != 0 && (sw.mapgen < 0 ? !(stt.mg_max > 1u && cx->mapgen_dense) : sw.mapgen != 0) && !cx->mapgen_off && cx->mapgen_voids < 2;
-    pl.sym_mode = !is_guided(family) ? 0 : (p->gt.sym_bits == 4 && !sw.no_g16 ? 2 : 1);
+    pl.sym_mode = !is_guided(family) ? 0 : (guided_sym_bits(*p) == 4 ? 2 : 1);
     if (pl.direct) pl.n_chunks = (args.vend + pl.lane_bytes * direct_block_threads() - 1) / (pl.lane_bytes * direct_block_threads());
     // Exact sub-ranges (round 5): every lane walks the bytes of its sub-range and nothing else, from the state the transducer is in
     // there — what makes a line of 400 KB as parallel as 4 000 lines of 100 bytes (rounds 1-4: a lane owns the lines that START in its
@@ -1838,6 +1844,12 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
         }
         if (p->stt.ok) serialize_stream(p->stt, p->sblob);
         if (p->gt.ok) { serialize_stream(p->gt.fwd, p->gblob); serialize_rev(p->gt, p->rblob); }
+        if (p->gt.ok && !p->gt.accept.empty()) {
+            std::vector<uint32_t> bits((p->gt.accept.size() + 31) / 32, 0u);
+            for (size_t y = 0; y < p->gt.accept.size(); ++y)
+                if (p->gt.accept[y]) bits[y >> 5] |= 1u << (y & 31);
+            put(p->ablob, 0, bits.data(), bits.size());
+        }
         *out = p.release();
         return TRRE_OK;
     } catch (const Error& e) {
@@ -1873,7 +1885,7 @@ void trre_free(trre_prog* p) {
     for (auto& kv : p->dev) {
         DeviceState& st = *kv.second;
         (void)hipSetDevice(st.device);
-        for (void* b : {(void*)st.d_blob, (void*)st.d_sblob, (void*)st.d_gblob, (void*)st.d_rblob, (void*)st.d_nblob, (void*)st.d_kblob}) (void)hipFree(b);
+        for (void* b : {(void*)st.d_blob, (void*)st.d_sblob, (void*)st.d_gblob, (void*)st.d_rblob, (void*)st.d_nblob, (void*)st.d_kblob, (void*)st.d_ablob}) (void)hipFree(b);
         (void)hipFree(st.d_lent); (void)hipFree(st.d_lpool); (void)hipFree(st.d_lcls);
         for (void* r : st.retired) (void)hipFree(r);
         ctx_free(st.ctx);
@@ -1940,6 +1952,7 @@ size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap) { re
 
 size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap) {
     if (!p) return 0;
+    if (which == 4) return export_blob(p->gt.accept, buf, cap);       // (match mode: a byte per backward state, 1: a line that starts with the symbol is accepted)
     return export_blob(which == 0 ? p->rblob : (which == 2 ? p->nblob : (which == 3 ? p->kblob : p->gblob)), buf, cap);   // (2: the enumeration's / the backtracking fallback's tables, 3: the stack guard's)
 }
 
@@ -2389,6 +2402,144 @@ int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     std::lock_guard<std::mutex> lock(st->mu);
     if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
     return strings_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
+}
+
+// ---- matched strings (records_block.hpp) -----------------------------------------------------------------------------------
+// d_rec as for the strings call; d_match: cnt [groups], base [groups + 1] of the verdicts, kept until the final offsets
+static int match_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
+                    size_t cap, int64_t* d_out_off, uint64_t* d_valid, size_t* n_matched, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    const int64_t T = str_tile_bytes();
+    const int64_t total = (int64_t)(n + nrec);                     // the staged text
+    const int64_t tiles = (total + T - 1) / T;
+    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
+    int rc;
+    // 1. the offsets, on the device: nothing is written before they pass
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
+    const int bad = rec_status(cx, s, nullptr, nullptr);
+    if (bad < 0) return TRRE_E_DEVICE;
+    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 2. the staged text, as for the strings call; its '\n' are the strings' closing ones and nothing else exactly when their number is nrec
+    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    StrArgs sa{};
+    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
+    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = d_out_off;
+    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
+    launch_str_part(0, sa, part, tiles, s);
+    launch_str_stage(sa, tiles, s);
+    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    uint64_t staged_nl = 0;
+    if (rec_status(cx, s, const_cast<uint64_t*>(sa.base) + tiles, &staged_nl) < 0) return TRRE_E_DEVICE;
+    if (staged_nl != nrec) return fail(TRRE_E_ARG, "error: a string holds a newline: it would be several lines with several verdicts");
+    // 3. the plain match scan of the staged text into the framed buffer, on the general guided family: its count pass always runs, and with
+    // it the backward pass, whose symbols the verdicts are read from (the length-preserving family does not launch into too small a buffer)
+    const size_t fcap = cap + nrec;
+    HIP_TRY(cx->d_framed.reserve(fcap + 64, fcap + 64));
+    rc = enqueue(p, st, cx, TRRE_KERNEL_GUIDED_GEN, cx->d_snap, (size_t)total, cx->d_framed, fcap, s);
+    if (rc) { cx->pend = Pending(); return rc; }
+    size_t m = 0;
+    rc = finish(p, st, cx, &m);
+    if (rc && rc != TRRE_E_CAPACITY) return rc;            // (TRRE_E_DIVERGES: *out_len stays 0)
+    // 4. the verdicts: the bitmap, M_i in out_off[i + 1], n_matched
+    const int64_t groups = ((int64_t)nrec + kMatchThreads - 1) / kMatchThreads;
+    HIP_TRY(cx->d_match.reserve((size_t)groups, (size_t)(2 * groups + 1) * 8));
+    MatchArgs ma{};
+    ma.sym_v0 = cx->d_sym; ma.vbeg = (int64_t)(reinterpret_cast<uintptr_t>(cx->d_snap.p) & 15u);
+    ma.off = d_off; ma.nrec = (int64_t)nrec;
+    ma.accept = reinterpret_cast<const uint32_t*>(st->d_ablob); ma.accept_words = (uint32_t)(p->ablob.size() / 4);
+    ma.valid = d_valid; ma.words = ((int64_t)nrec + 63) / 64;
+    ma.out_off = d_out_off; ma.cnt = cx->d_match; ma.base = cx->d_match + groups;
+    launch_match_verdict(guided_sym_bits(*p), ma, s);
+    launch_chunk_scan(ma.cnt, const_cast<uint64_t*>(ma.base), groups, s);
+    launch_match_rank(ma, s);
+    HIP_TRY(hipGetLastError());
+    uint64_t matched = 0;
+    if (rec_status(cx, s, const_cast<uint64_t*>(ma.base) + groups, &matched) < 0) return TRRE_E_DEVICE;
+    if (n_matched) *n_matched = (size_t)matched;
+    const size_t need = m >= matched ? m - (size_t)matched : 0;
+    if (rc == TRRE_E_CAPACITY || need > cap) {
+        if (out_len) *out_len = need;
+        return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    }
+    if (m == 0) {                                           // nothing accepted (an accepted string prints at least its framing '\n')
+        if (matched) return fail(TRRE_E_DEVICE, "error: the matched strings' output offsets do not add up (internal)");
+        HIP_TRY(hipMemsetAsync(d_out_off, 0, (nrec + 1) * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 5. string i's framed output ends just past framed newline number M_i
+    const int64_t RT = rec_tile_bytes();
+    const int64_t otiles = ((int64_t)m + RT - 1) / RT, utiles = ((int64_t)m + T - 1) / T;
+    HIP_TRY(rec_room(cx, utiles));                          // (the compaction's tiles are the smaller ones: room for both)
+    RecArgs oa{};
+    oa.in_v0 = cx->d_framed; oa.vbeg = 0; oa.vend = (int64_t)m; oa.nrec = (int64_t)nrec; oa.out_off = d_out_off;
+    rec_carve(cx, otiles, oa);
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_count(oa, otiles, s);
+    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
+    launch_rec_part(1, oa, otiles, s);
+    launch_rec_locate(oa, otiles, d_bad, s);
+    uint64_t last[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&last[1], oa.base + otiles, 8, hipMemcpyDeviceToHost, s));
+    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(d_out_off + nrec), &last[0]);
+    if (lost < 0) return TRRE_E_DEVICE;
+    if (lost || last[0] != m || last[1] != matched) return fail(TRRE_E_DEVICE, "error: the matched strings' output offsets do not add up (internal)");
+    // 6. the final offsets; the framed output without its newlines into the caller's buffer
+    launch_match_final(ma, s);
+    RecArgs ca{};
+    ca.in_v0 = cx->d_framed; ca.vbeg = 0; ca.vend = (int64_t)m;
+    rec_carve(cx, utiles, ca);
+    launch_match_count(ca, utiles, s);
+    launch_chunk_scan(ca.cnt, const_cast<uint64_t*>(ca.base), utiles, s);
+    StrArgs ua{};
+    ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - matched);
+    ua.nrec = (int64_t)nrec; ua.out_off = d_out_off;
+    ua.part = reinterpret_cast<const int64_t*>(ca.base);
+    launch_match_unframe(ua, utiles, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_len) *out_len = m - (size_t)matched;
+    return TRRE_OK;
+}
+
+int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                              int64_t* d_out_off, uint8_t* d_valid, size_t* n_matched, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_matched) *n_matched = 0;
+    if (!p || !d_off || !d_out_off || (n && !d_in) || (cap && !d_out) || (nrec && !d_valid)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_MATCH) return fail(TRRE_E_ARG, "error: matched strings take a program compiled with TRRE_MODE_MATCH");
+    if (p->prints_newline)
+        return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: record outputs could not be told apart");
+    if (!p->gt.ok || p->ablob.empty() || p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: the verdicts come from the guided tables, which this program does not have or was told not to use (the backtracking family)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    if (reinterpret_cast<uintptr_t>(d_valid) & 7u) return fail(TRRE_E_ARG, "error: the validity bitmap must be 8-byte aligned (it is written as 64-bit words)");
+    if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
+    const size_t ob = (nrec + 1) * 8, vb = (nrec + 63) / 64 * 8;
+    if (ranges_overlap(d_off, ob, d_out_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
+        ranges_overlap(d_out_off, ob, d_in, n) || ranges_overlap(d_out_off, ob, d_out, cap))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or the other offsets array");
+    if (ranges_overlap(d_valid, vb, d_in, n) || ranges_overlap(d_valid, vb, d_out, cap) || ranges_overlap(d_valid, vb, d_off, ob) ||
+        ranges_overlap(d_valid, vb, d_out_off, ob))
+        return fail(TRRE_E_ARG, "error: the validity bitmap overlaps the data or an offsets array");
+    DeviceState* st;
+    int rc = current_state(p, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return match_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_matched, out_len,
+                    static_cast<hipStream_t>(stream));
 }
 
 namespace {

@@ -1669,6 +1669,112 @@ unsigned rec_grid(int64_t items) {
     return (unsigned)(blocks < 1 ? 1 : blocks > 256 * 16 ? 256 * 16 : blocks);
 }
 
+// ---- matched strings (records_block.hpp; runtime.cpp: trre_match_device_strings) -------------------------------------------
+static_assert(kMatchThreads == 4 * kWave && kMatchThreads == SG::THREADS, "a group is four bitmap words; rec_block_scan");
+
+// A workgroup takes groups of kMatchThreads consecutive strings in turn, a wave 64 of them: lane k loads off[i] (coalesced), reads the
+// symbol at the string's first staged byte (a gather: one sector per string) and looks it up in the accept bits, which all threads
+// stage into LDS once, with the barrier between the staging and the first lookup.  The wave's verdicts are one ballot — the bitmap
+// word, stored by lane 0; lanes at or beyond nrec vote false, so the bitmap's tail is zero.
+template <int kBits>
+__global__ __launch_bounds__(kMatchThreads) void k_match_verdict(MatchArgs a, int64_t groups) {
+    __shared__ uint32_t acc[512];                    // 16 384 backward states at most (front.hpp: GuidedLimits)
+    __shared__ uint32_t wtot[kMatchThreads / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    for (uint32_t k = tid; k < a.accept_words && k < 512u; k += kMatchThreads) acc[k] = a.accept[k];
+    __syncthreads();
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const int64_t i = g * kMatchThreads + tid;
+        const bool ok = i < a.nrec && match_verdict<kBits>(a, acc, i);
+        const uint64_t word = __ballot(ok);
+        if (lane == 0) {
+            const int64_t at = g * (kMatchThreads / kWave) + w;
+            if (at < a.words) a.valid[at] = word;
+            wtot[w] = match_popc64(word);
+        }
+        __syncthreads();
+        uint32_t below = 0, total = 0;
+        for (int k = 0; k < kMatchThreads / kWave; ++k) {
+            const uint32_t t = wtot[k];
+            below += k < w ? t : 0u;
+            total += t;
+        }
+        match_park(a, i, below, word, lane);
+        if (tid == 0) a.cnt[g] = total;
+        __syncthreads();                             // (wtot is the next group's too)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_match_rank(MatchArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) match_add_base(a, i);
+}
+
+__global__ __launch_bounds__(256) void k_match_final(MatchArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) match_final(a, i);
+}
+
+// '\n' per tile of the compaction (k_rec_count on the strings' 16 KiB tiles)
+__global__ __launch_bounds__(SG::THREADS) void k_match_count(RecArgs a) {
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const uint64_t c = wave_sum(rec_count_vecs<SG>(a, blockIdx.x, threadIdx.x, nullptr));
+    if ((threadIdx.x & (kWave - 1)) == 0) wtot[threadIdx.x / kWave] = (uint32_t)c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (int k = 0; k < SG::THREADS / kWave; ++k) t += wtot[k];
+        a.cnt[blockIdx.x] = t;
+    }
+}
+
+// k_str_unframe with the marks from the bytes: a.part holds the '\n' before every tile, so a tile's destination starts at
+// s0 - part[b], and no offset is touched
+__global__ __launch_bounds__(SG::THREADS) void k_match_unframe(StrArgs a) {
+    __shared__ U128 lds[SG::NVEC + 2];
+    __shared__ uint32_t bits32[SG::NVEC / 2];
+    __shared__ uint32_t pv[SG::NVEC + 1];
+    __shared__ uint16_t inv[SG::NVEC + 2];
+    __shared__ uint32_t pre[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const StrTile<SG> t(a, blockIdx.x, false);
+    U128 w[SG::VECS + 1];
+    str_load_vecs<SG>(a, t, tid, w);
+    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
+    match_mark_vecs<SG>(t, tid, w, bits16);
+    str_keep_vecs<SG>(t, tid, w, lds);
+    __syncthreads();
+    const uint32_t marks = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
+    str_fill_pv<SG>(bits16, pre[tid], tid, pv);
+    __syncthreads();
+    const StrOut<SG> o(a, t, marks);
+    str_fill_inv<SG>(t, o, tid, bits16, pv, inv);
+    __syncthreads();
+    str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
+}
+
+void launch_match_verdict(int sym_bits, const MatchArgs& a, void* stream) {
+    const int64_t groups = (a.nrec + kMatchThreads - 1) / kMatchThreads;
+    const dim3 grid((unsigned)(groups < 1 ? 1 : groups > 256 * 16 ? 256 * 16 : groups)), block(kMatchThreads);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (sym_bits == 4) hipLaunchKernelGGL(k_match_verdict<4>, grid, block, 0, s, a, groups);
+    else if (sym_bits == 16) hipLaunchKernelGGL(k_match_verdict<16>, grid, block, 0, s, a, groups);
+    else hipLaunchKernelGGL(k_match_verdict<8>, grid, block, 0, s, a, groups);
+}
+void launch_match_rank(const MatchArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_match_rank, dim3(rec_grid(a.nrec)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_match_final(const MatchArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_match_final, dim3(rec_grid(a.nrec)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_match_count(const RecArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_match_count, dim3((unsigned)tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_match_unframe(const StrArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_match_unframe, dim3((unsigned)tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+
 int64_t rec_tile_bytes() { return RG::TILE; }
 void launch_rec_check(const int64_t* off, int64_t nrec, int64_t n, uint32_t* status, void* stream) {
     hipLaunchKernelGGL(k_rec_check, dim3(rec_grid(nrec + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), off, nrec, n, status);
