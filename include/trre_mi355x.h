@@ -50,6 +50,9 @@ extern "C" {
                                  count, exclusive sum, emit: trre_amd/csrc/gen_block.hpp —; the host enumeration of round 3
                                  (trre_amd/csrc/generate.cpp) takes a chunk on which a path never returns or a search
                                  outgrows a lane's stack. */
+#define TRRE_MODE_FIND 4 /* every match of every string, the rest thrown away (findall, grep -o): the outputs of the scan loop's
+                          * successful attempts (trre_nft.c:775-790) as a list per string.  NFT engine only; runs through
+                          * trre_find_device_strings and nothing else */
 
 /* return codes */
 #define TRRE_OK 0
@@ -139,7 +142,7 @@ int trre_set_kernel(trre_prog* p, int kernel_family); /* force a family (benchma
  * tests).  Returns the blob size; copies min(size, cap) bytes. */
 size_t trre_export_tables(const trre_prog* p, void* buf, size_t cap);
 size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap); /* 0 if the pattern does not fold */
-size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted; 0 if none */
+size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted, 5 / 6 (find mode) the texts / the marks forward tables, both over the backward DFA of 0; 0 if none */
 
 /* Replaces the scan branch of main() (trre_nft.c:775-790 / trre_dft.c:1272-1286)
  * for a whole buffer that is already resident in HBM.
@@ -241,6 +244,46 @@ int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
  * workspace, 16 bytes per 256 strings.  Synchronous with respect to `stream`; trre_last_scan_flags as for the strings call. */
 int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
                               size_t cap, int64_t* d_out_off, uint8_t* d_valid, size_t* n_matched, size_t* out_len, void* stream);
+
+/* Found strings: the same column of strings under a program compiled with TRRE_MODE_FIND — every match of every string, the
+ * rest thrown away (re.findall, grep -o, str.extract_all).  For a string s that holds no '\n', let L be s cut at its first NUL.
+ * The reference's scan loop (trre_nft.c:775-790) runs an attempt at position 0 of L; an attempt that reaches FINAL prints its
+ * output o; if it consumed k > 0 bytes the next attempt starts k bytes on, otherwise one raw byte is copied and the next attempt
+ * starts one byte on; one more attempt runs on the empty tail.  find(s) is the list of all those o, in order, the raw bytes
+ * gone — attempts that consumed nothing included ('x*' on "bb": three empty matches, as Python's findall), an o being what
+ * fputs prints (an output that holds a NUL ends before it).  A string without a successful attempt has an empty list.
+ * With A = 0x01, B = 0x02 and W = (:A)(P)(:B), find(s) is the pieces between A and B of what the reference prints for W on s.
+ *   d_list_off   nrec + 1 entries: d_list_off[i] is the number of matches in strings 0 .. i - 1, d_list_off[nrec] = *n_matches
+ *   d_match_off  room for match_cap + 1 entries: entry j is where match j's output starts in d_out, entry *n_matches = *out_len
+ *   d_out        cap bytes: the outputs, concatenated
+ * *n_matches may be null.  nrec == 0 is valid with n == 0: d_list_off[0] = 0, and d_match_off[0] = 0 if d_match_off is not null.
+ * Arguments, overlaps (the two offset arrays are two more arrays that overlap nothing), d_in == d_out, d_out null with cap == 0,
+ * d_match_off null with match_cap == 0, the offsets' check (TRRE_E_ARG, nothing written) and a split-form scan in flight: as
+ * for trre_match_device_strings.  A string that holds a '\n' would be several lines: TRRE_E_ARG, found on the device from the
+ * staged text's newline count before anything of the caller's is written.
+ * Refused before the device is touched: a program not compiled with TRRE_MODE_FIND (TRRE_E_ARG) — and a find program given to
+ * any other scan call (TRRE_E_ARG) —; one that can print a '\n' of its own (TRRE_E_UNSUPPORTED); TRRE_KERNEL_BACKTRACK forced
+ * through trre_set_kernel (TRRE_E_UNSUPPORTED).  Refused by trre_compile_mode (TRRE_E_UNSUPPORTED): TRRE_ENGINE_DFT (the
+ * identity above does not hold for the deterministic engine: nothing to test it against) and a pattern without guided tables.
+ * Both scans run on the general guided family (trre_info.kernel: TRRE_KERNEL_GUIDED_GEN); the stack guard applies as in scan mode.
+ *   TRRE_E_CAPACITY  exactly when the outputs need more than cap bytes or there are more than match_cap matches; *out_len and
+ *                    *n_matches hold what is needed and d_list_off is valid.  d_out and d_match_off have not been written at
+ *                    all (in place the input is intact): cap == 0 and match_cap == 0 with both null is the size query, and
+ *                    a retry with room works.
+ *   TRRE_E_DIVERGES  *out_len = 0; the arrays are unspecified; trre_last_error() holds the reference's message.
+ * How: the strings call's staged text is scanned twice on the general guided family, under two forward tables over one backward
+ * automaton.  The marks table prints one byte per match and each line's '\n': unframed by the strings call's passes, its
+ * offsets are d_list_off.  The texts table prints every match's output and a '\n' behind it: framed newline number j at framed
+ * position q closes match j, d_match_off[j + 1] = q - j, and the framed text goes into d_out with every '\n' dropped.
+ * Device memory, kept by the (prog, device) until trre_free: the staged text, n + nrec + 64 bytes; the framed marks and the
+ * marks unframed, n_matches + nrec + 64 and n_matches + 64 bytes (at least n + nrec + 64); the framed texts, *out_len + n_matches
+ * + 64 bytes (at least n + nrec + 64) — these two grow on the size a scan reports, which costs the first call on a larger
+ * column one more scan —; 8 (nrec + 1) bytes of list offsets; 24 bytes per 16 KiB of the staged and the framed texts; and the
+ * general guided family's workspace twice (each scan has its own: symbols, 1 byte per staged byte — half a byte up to 16
+ * backward states, 2 bytes beyond 256 —, and lane counts).  Synchronous with respect to `stream`; trre_last_scan_flags as for
+ * the strings call. */
+int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                             int64_t* d_match_off, size_t match_cap, int64_t* d_list_off, size_t* n_matches, size_t* out_len, void* stream);
 
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */

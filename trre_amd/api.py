@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRRE_LIB_PATH") or os.path.join(_HERE, "lib", "libtrre_mi355x.so")   # override: A/B builds only
 
 ENGINE_NFT, ENGINE_DFT = 0, 1
-MODE_SCAN, MODE_MATCH, MODE_SCAN_ALL, MODE_MATCH_ALL = 0, 1, 2, 3
+MODE_SCAN, MODE_MATCH, MODE_SCAN_ALL, MODE_MATCH_ALL, MODE_FIND = 0, 1, 2, 3, 4
 _ENGINES = {"nft": ENGINE_NFT, "dft": ENGINE_DFT, ENGINE_NFT: ENGINE_NFT, ENGINE_DFT: ENGINE_DFT}
 
 KERNEL_AUTO, KERNEL_BYTEMAP, KERNEL_TILE_LP, KERNEL_TILE_GEN, KERNEL_STREAM_LP, KERNEL_STREAM_GEN = 0, 1, 2, 3, 4, 5
@@ -95,6 +95,7 @@ def lib():
         L.trre_scan_device_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_scan_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_match_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_find_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -124,10 +125,12 @@ class Program:
 
     def __init__(self, pattern, engine="nft", mode="scan"):
         """mode "scan" (default), "match" (`trre -m`: whole-line matches only, NFT engine), "scan_all" (`trre -a`) or
-        "match_all" (`trre -ma`): generator modes, every accepting path prints (NFT engine)"""
+        "match_all" (`trre -ma`): generator modes, every accepting path prints (NFT engine), or "find": every match of every
+        string as a list per string (find_strings / find_list, NFT engine)"""
         self.pattern = _bytes(pattern)
         self.engine = _ENGINES[engine]
-        self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL}.get(mode, mode)
+        self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL,
+                     "find": MODE_FIND}.get(mode, mode)
         self._h = ctypes.c_void_p()
         _check(lib().trre_compile_mode(self.pattern, len(self.pattern), self.engine, self.mode, ctypes.byref(self._h)))
 
@@ -176,6 +179,18 @@ class Program:
         buf = ctypes.create_string_buffer(max(n, 1))
         lib().trre_export_guided_tables(self._h, 4, buf, n)
         return buf.raw[:n]
+
+    def export_find_tables(self):
+        """find mode: (backward DFA blob, texts forward tables blob, marks forward tables blob), or (b"", b"", b"")"""
+        blobs = []
+        for which in (0, 5, 6):
+            n = lib().trre_export_guided_tables(self._h, which, None, 0)
+            buf = ctypes.create_string_buffer(max(n, 1))
+            lib().trre_export_guided_tables(self._h, which, buf, n)
+            blobs.append(buf.raw[:n])
+        if not blobs[1]:
+            return (b"", b"", b"")
+        return tuple(blobs)
 
     def export_gen_tables(self):
         """generator modes: the tables of the device enumeration (gen_block.hpp), or b"" """
@@ -351,6 +366,48 @@ class Program:
         o = out_off.cpu().numpy().tolist()
         ok = valid.cpu().numpy().tolist()
         return [blob[o[i]:o[i + 1]] if ok[i] else None for i in range(len(recs))]
+
+    def find_strings(self, values, offsets, stream=None):
+        """Found strings (trre_find_device_strings; a program compiled with mode="find"): values and offsets as for
+        scan_strings, no string holding a b"\\n".  Returns (out, match_offsets, list_offsets): string i's matches are numbers
+        list_offsets[i] .. list_offsets[i + 1] - 1, and match j's output is out[match_offsets[j]:match_offsets[j + 1]].  Two
+        calls: the size query, then the one that fills buffers of exactly that size."""
+        import torch
+        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
+        n, nrec = values.numel(), offsets.numel() - 1
+        list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
+        m, k = ctypes.c_size_t(), ctypes.c_size_t()
+
+        def call(o, cap, mo, mcap):
+            return lib().trre_find_device_strings(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o, cap, mo, mcap,
+                                                  list_off.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
+        with torch.cuda.device(values.device):
+            rc = call(None, 0, None, 0)
+            if rc not in (0, E_CAPACITY):
+                _check(rc)
+            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
+            match_off = torch.zeros(k.value + 1, dtype=torch.int64, device=values.device)
+            if rc == E_CAPACITY:
+                _check(call(out.data_ptr(), m.value, match_off.data_ptr(), k.value))
+        return out[:m.value], match_off, list_off
+
+    def find_list(self, records, device=0):
+        """list of bytes in -> list of lists of bytes out: every match's output, string by string (through find_strings)"""
+        import numpy as np
+        import torch
+        recs = [_bytes(r) for r in records]
+        off = np.zeros(len(recs) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in recs], out=off[1:])
+        dev = torch.device("cuda", device)
+        packed = b"".join(recs)
+        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
+        out, match_off, list_off = self.find_strings(values, torch.from_numpy(off).to(dev))
+        blob = out.cpu().numpy().tobytes()
+        mo = match_off.cpu().numpy().tolist()
+        lo = list_off.cpu().numpy().tolist()
+        return [[blob[mo[j]:mo[j + 1]] for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
 
     @staticmethod
     def _map_list(records, device, scan):

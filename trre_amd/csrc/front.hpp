@@ -405,6 +405,13 @@ struct GuidedTables {
 // byte, accepted only if it ends exactly at the end of the line; an accepted line prints its output and '\n', a
 // rejected one prints nothing.
 GuidedTables build_guided_nft(const NftNodes& nodes, const GuidedLimits& lim = GuidedLimits());
+// Find mode (TRRE_MODE_FIND; nodes as for scan mode): two forward tables over ONE backward DFA, both walking the scan loop.
+//   texts   a raw byte prints nothing, every attempt that reaches FINAL prints its output and '\n', the end of a line nothing:
+//           the scan of a text is its matches' outputs, each closed by a '\n'
+//   marks   every attempt that reaches FINAL prints one byte ('m'), a raw byte nothing, the end of a line its '\n':
+//           the scan of a text is, line by line, as many bytes as the line has matches
+// Both or neither (false: beyond the limits); texts.sym_bits == marks.sym_bits, so the backward blob is one.
+bool build_guided_find(const NftNodes& nodes, GuidedTables& texts, GuidedTables& marks, const GuidedLimits& lim = GuidedLimits());
 // The deterministic engine in the same form (trre_dft.c:1110-1196): the backward DFA says at every position what becomes of an
 // attempt from START there (and which class the byte has), the forward transducer walks the determinised tables only through
 // attempts that succeed.  For patterns whose scan loop does not fold into a stream table (a loop before the decision:

@@ -98,6 +98,23 @@ public:
         return g;
     }
 
+    // find mode (front.hpp: build_guided_find): one backward DFA, the texts table and the marks table over it.  The symbols'
+    // layout is one for both (nibbles only when both forward tables have the small form): one backward blob serves the two.
+    void run_find(GuidedTables& texts, GuidedTables& marks) {
+        GuidedTables g;
+        byte_classes(g);
+        backward(g);
+        marks = g;
+        find_ = kFindTexts;
+        forward(g);
+        find_ = kFindMarks;
+        forward(marks);
+        g.wide = marks.wide = g.n_rev > 256;
+        g.sym_bits = marks.sym_bits = g.wide ? 16 : ((g.n_rev <= 16 && g.fwd.g16_ok && marks.fwd.g16_ok) ? 4 : 8);
+        g.ok = marks.ok = true;
+        texts = std::move(g);
+    }
+
 private:
     // match mode: which symbols at a line's first byte mean "accepted" — the root cell's own question (match_cell, s == 0): does
     // the start list hold an entry the search does not get past.  (An entry that diverges counts: such a line never reaches the
@@ -206,6 +223,7 @@ private:
         const RevSets& r = rev_[y];
         const bool at_end = y == kSymEol || y == kSymNul;
         if (match_) return match_cell(s, y, r, at_end);
+        if (find_) return find_cell(s, y, r, at_end);
         const std::vector<NodeFollow>& start = nd_.follow[n_nodes_];
         bool fresh = s == 0;
         bool muted = fresh ? false : (fwd_[s] & 1) != 0;
@@ -291,9 +309,64 @@ private:
         return c;
     }
 
+    // Find mode (trre_find_device_strings): cell()'s walk of the scan loop, printing only what a FINAL prints.  A raw byte prints
+    // nothing (the two copy_c branches of cell(): no match here, an empty attempt inside the line); the echo of a copy-mode
+    // node is part of its attempt's output and stays.
+    //   texts   every FINAL — fresh or not, on the empty tail too — appends '\n' behind the attempt's output (a muted attempt's
+    //           output ended at its NUL: fputs); the end of the line prints nothing
+    //   marks   every FINAL prints one byte, 'm', in place of the attempt's output, which is not printed at all; the end of the
+    //           line prints its '\n' as in scan mode
+    // next, eol and the diverging cells are cell()'s.
+    StreamCell find_cell(uint32_t s, uint32_t y, const RevSets& r, bool at_end) {
+        StreamCell c;
+        const bool texts = find_ == kFindTexts;
+        const std::vector<NodeFollow>& start = nd_.follow[n_nodes_];
+        bool fresh = s == 0;
+        bool muted = fresh ? false : (fwd_[s] & 1) != 0;
+        const std::vector<NodeFollow>* cur = fresh ? &start : &nd_.follow[fwd_[s] / 2];
+        bool ended = false;
+        for (;;) {
+            const int e = decisive(*cur, r, true);
+            if (e < 0) {
+                if (!fresh) { c.diverge = true; c.next = 1; c.out.clear(); return c; }     // cannot happen (cell())
+                if (at_end) { ended = true; break; }
+                c.next = 0;          // no match here: the raw byte is dropped
+                break;
+            }
+            const NodeFollow& f = (*cur)[e];
+            if (diverges(f, r)) { c.diverge = true; c.next = 2; return c; }
+            if (f.target == kNodeFinal) {
+                if (texts && !muted) c.out += f.out;
+                c.out.push_back(texts ? '\n' : 'm');
+                if (fresh) {         // an attempt that consumed nothing
+                    if (at_end) { ended = true; break; }
+                    c.next = 0;      // ... inside the line: the raw byte behind it is dropped
+                    break;
+                }
+                fresh = true;
+                muted = false;
+                cur = &start;
+                continue;
+            }
+            if (texts && !muted) c.out += f.out;
+            if (f.mute) muted = true;
+            if (texts && nd_.node[f.target].echo && !muted) c.copy_c = true;
+            c.next = intern_fwd(f.target, muted);
+            break;
+        }
+        if (ended) {
+            if (!texts) c.out.push_back('\n');
+            c.next = y == kSymNul ? 1u : 0u;
+            c.eol = y == kSymEol;
+        }
+        if (c.out.size() > lim_.max_out) throw StreamGiveUp();
+        return c;
+    }
+
     void forward(GuidedTables& g) {
         StreamPackInput in;
         fwd_.assign(3, 0);
+        fwd_index_.clear();                                 // (find mode runs this twice)
         in.wide_cols = g.n_rev > 256;
         for (uint32_t s = 0; s < fwd_.size(); ++s) {        // (fwd_ grows while we go)
             if ((uint64_t)(s + 1) * g.n_rev > lim_.max_fwd_cells) throw StreamGiveUp();
@@ -302,13 +375,15 @@ private:
             for (uint32_t y = 0; y < g.n_rev; ++y) row.push_back(cell(s, y));
             in.rows.push_back(std::move(row));
         }
-        g.fwd = pack_forward(in, g.n_rev, match_);
+        g.fwd = pack_forward(in, g.n_rev, match_ || find_ != 0);
     }
 
     const NftNodes& nd_;
     GuidedLimits lim_;
     uint32_t n_nodes_;
     bool match_;
+    enum : int { kFindTexts = 1, kFindMarks = 2 };
+    int find_ = 0;                                  // 0: scan / match mode (cell, match_cell); else which table find_cell builds
     std::vector<int> rep_;                          // class -> a representative byte
     std::vector<std::vector<uint32_t>> readers_;    // class -> nodes that read its bytes
     std::vector<RevSets> rev_;
@@ -587,6 +662,16 @@ GuidedTables build_guided_nft(const NftNodes& nodes, const GuidedLimits& lim) {
         return GuidedBuilder(nodes, lim).run();
     } catch (const StreamGiveUp&) {
         return GuidedTables();        // ok == false
+    }
+}
+
+bool build_guided_find(const NftNodes& nodes, GuidedTables& texts, GuidedTables& marks, const GuidedLimits& lim) {
+    try {
+        GuidedBuilder(nodes, lim).run_find(texts, marks);
+        return true;
+    } catch (const StreamGiveUp&) {
+        texts = marks = GuidedTables();
+        return false;
     }
 }
 

@@ -104,6 +104,9 @@ void launch_match_rank(const MatchArgs& a, void* stream);
 void launch_match_final(const MatchArgs& a, void* stream);
 void launch_match_count(const RecArgs& a, int64_t tiles, void* stream);
 void launch_match_unframe(const StrArgs& a, int64_t tiles, void* stream);
+// found strings (records_block.hpp): launch_match_unframe's compaction and the matches' offsets (a.part: the '\n' before every tile,
+// a.out_off: match_off, a.nrec: the number of matches)
+void launch_find_unframe(const StrArgs& a, int64_t tiles, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

@@ -594,4 +594,34 @@ TRRE_HD void match_mark_vecs(const StrTile<G>& t, int tid, const U128 (&w)[G::VE
     }
 }
 
+// ---- found strings (trre_find_device_strings) ------------------------------------------------------------------------------
+// A find-mode program pulls every match out of every string: find(s) is the list of the outputs of the scan loop's successful
+// attempts on the line s (trre_nft.c:775-790), the raw bytes gone.  Two scans of the strings call's staged text, under the two
+// forward tables of guided_build.cpp: find_cell, give everything:
+//   marks   per line one byte per match and the line's '\n': the strings call's own unframing of it leaves, as ITS output
+//           offsets, the list offsets — list_off[i] = matches in strings 0 .. i - 1, list_off[nrec] = n_matches
+//   texts   every match's output closed by a '\n' (the program prints none of its own): framed newline number j (0-based), at
+//           framed position q, closes match j, so match_off[j + 1] = q - j, match_off[0] = 0, and the output bytes are the
+//           framed text with every '\n' dropped — k_match_unframe's compaction.
+// The passes behind the two scans: k_match_count, k_chunk_scan ('\n' per framed tile and before it; the total is n_matches
+// again) and k_find_unframe: k_match_unframe plus the offsets.  Who writes which word: match_off[0] one thread of tile 0; every
+// other word the lane that owns its newline, once.  A wave takes 64 framed bytes at a time: their marks are one 64-bit word
+// (what a ballot of "my byte is a '\n'" gives, read from the tile's mark image instead), the rank of a lane's newline is the
+// marks before the piece (pv, from the workgroup's scan: wave_scan_incl) plus the set bits below the lane, so the lanes of a
+// wave store adjacent words for adjacent ranks — when every framed byte is a '\n' (every match empty) a wave's 64 stores are
+// 512 contiguous bytes, and a tile's 16 384 offsets take 64 such rounds of its four waves.
+template <class G>
+TRRE_HD void find_offset_vecs(const StrArgs& a, const StrTile<G>& t, int tid, const uint16_t* bits16, const uint32_t* pv) {
+    constexpr int kPieces = G::NVEC / 4, kWaves = G::THREADS / 64;
+    const int lane = tid & 63;
+    if (t.s0 == 0 && tid == 0) a.out_off[0] = 0;
+    for (int k = tid >> 6; k < kPieces; k += kWaves) {
+        const uint64_t word = (uint64_t)bits16[4 * k] | (uint64_t)bits16[4 * k + 1] << 16 | (uint64_t)bits16[4 * k + 2] << 32 |
+                              (uint64_t)bits16[4 * k + 3] << 48;
+        if (!((word >> lane) & 1u)) continue;
+        const int64_t j = t.i0 + (int64_t)pv[4 * k] + (int64_t)match_popc64(word & ((1ull << lane) - 1ull));
+        if (j < a.nrec) a.out_off[j + 1] = t.s0 + 64 * (int64_t)k + lane - j;       // (never beyond: the newline total was checked before)
+    }
+}
+
 }  // namespace trre

@@ -170,6 +170,8 @@ struct ScanCtx {
     DevBuf<uint8_t> d_gen_out;        // generator modes: the enumeration's output before it goes down (bytes)
     DevBuf<uint8_t> d_framed;         // trre_scan_device_strings: the scan's output with every record's closing '\n' still in it (bytes)
     DevBuf<uint64_t> d_match;         // trre_match_device_strings: accepted strings per group of 256, then their exclusive scan [groups + 1] (groups)
+    DevBuf<int64_t> d_find_off;       // trre_find_device_strings: the list offsets while they are ranks and located positions [nrec + 1] (entries)
+    DevBuf<uint8_t> d_find_marks;     // ... the marks scan unframed: a byte per match (bytes)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
     DevBuf<uint32_t> d_cevents, d_chdr;
@@ -263,6 +265,8 @@ struct trre_prog {
     trre::GuardTables guard;          // scan mode, NFT engine: which lines can exhaust the reference's stack (stack_guard.cpp)
     std::vector<uint8_t> kblob;
     std::vector<uint8_t> ablob;       // match mode, guided tables: GuidedTables::accept as bits (32-bit words; trre_match_device_strings)
+    std::unique_ptr<trre_prog> find_marks;    // find mode: this program holds the texts table (gt), the inner one the marks table over the same
+                                              // backward DFA — a program of its own, with its own device state (trre_find_device_strings)
     int mask_bytes = 0;
     bool profiling = false;
     std::atomic<float> last_ms{-1.f};
@@ -516,6 +520,7 @@ int general_family(const trre_prog& p, bool stream_ok) {
 
 int auto_family(const trre_prog& p) {
     using namespace trre;
+    if (p.mode == TRRE_MODE_FIND) return TRRE_KERNEL_GUIDED_GEN;      // (both scans of trre_find_device_strings: their outputs are no one's input length)
     if (p.lazy_only) return TRRE_KERNEL_DFT_LAZY;      // beyond the eager construction's caps: the tables grow with the input (lazy_block.hpp)
     if (p.engine == TRRE_ENGINE_DFT && (p.dt.flags & kFlagMemoryless)) return TRRE_KERNEL_BYTEMAP;
     // a stream table too large for LDS is walked through L1/L2 (<= 0.35 TB/s); guided tables with a small forward table
@@ -652,9 +657,10 @@ constexpr uint64_t kGuardBudget = 1ull << 23;              // search steps per l
 // leave undecided is SAID: TRRE_SCAN_GUARD_UNDECIDED in trre_last_scan_flags().
 constexpr uint64_t kGuardCallBudget = 1ull << 35;
 constexpr const char* kStackMsg = "error: stack max capacity reached";
+constexpr const char* kFindOnlyMsg = "error: a program compiled with TRRE_MODE_FIND runs through trre_find_device_strings only";
 constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
 bool guard_applies(const trre_prog& p, const ScanCtx& cx, size_t n) {
-    return !trre::switches().no_stack_guard && p.guard.on && !cx.guard_off && (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH) && n + 1 >= p.guard.l_min;
+    return !trre::switches().no_stack_guard && p.guard.on && !cx.guard_off && (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH || p.mode == TRRE_MODE_FIND) && n + 1 >= p.guard.l_min;
 }
 struct GuardHit {
     bool hit = false;
@@ -1712,7 +1718,9 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
     if (!out) return fail(TRRE_E_ARG, "error: null output handle");
     *out = nullptr;
     if (engine != TRRE_ENGINE_NFT && engine != TRRE_ENGINE_DFT) return fail(TRRE_E_ARG, "error: unknown engine");
-    if (mode != TRRE_MODE_SCAN && mode != TRRE_MODE_MATCH && !is_generate(mode)) return fail(TRRE_E_ARG, "error: unknown mode");
+    if (mode != TRRE_MODE_SCAN && mode != TRRE_MODE_MATCH && mode != TRRE_MODE_FIND && !is_generate(mode)) return fail(TRRE_E_ARG, "error: unknown mode");
+    if (mode == TRRE_MODE_FIND && engine != TRRE_ENGINE_NFT)
+        return fail(TRRE_E_UNSUPPORTED, "error: find mode is offered for the non-deterministic engine only (the deterministic engine's matches cannot be told from its raw bytes by the reference)");
     if (mode == TRRE_MODE_MATCH && engine != TRRE_ENGINE_NFT)
         return fail(TRRE_E_UNSUPPORTED, "error: match mode is offered for the non-deterministic engine only (trre_dft -m prints empty lines)");
     if (is_generate(mode) && engine != TRRE_ENGINE_NFT) return fail(TRRE_E_UNSUPPORTED, "Not supported yet");   // trre_dft.c:1227-1229
@@ -1793,6 +1801,34 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
                 p->bt_ok = true;
             }
             make_guard(true);
+        } else if (mode == TRRE_MODE_FIND) {
+            // trre_find_device_strings: the scan loop's nodes under two forward tables over one backward DFA (guided_build.cpp: find_cell).
+            // This program keeps the texts table; the marks table lives in an inner program, which also carries the stack guard — its
+            // scan runs first.  Nothing else can run a find program: no tables, no find (the backtracking lists are kept so that
+            // trre_set_kernel can name that family and the find call can refuse it)
+            const NftNodes nodes = build_nft_nodes(nft);
+            p->nft_nodes = (uint32_t)nodes.node.size();
+            std::unique_ptr<trre_prog> marks(new trre_prog);
+            if (!build_guided_find(nodes, p->gt, marks->gt))
+                return fail(TRRE_E_UNSUPPORTED, "error: find mode runs on the guided tables, and this pattern is beyond their limits (a backward automaton of more than 16 384 states)");
+            marks->engine = engine; marks->mode = mode;
+            marks->nft_states = p->nft_states; marks->nft_cons = p->nft_cons; marks->nft_nodes = p->nft_nodes;
+            marks->prints_newline = p->prints_newline;
+            serialize_stream(marks->gt.fwd, marks->gblob);
+            serialize_rev(marks->gt, marks->rblob);
+            {
+                GenTables lists;
+                lists.nodes = nodes;
+                lists.ok = true;
+                serialize_gen(lists, p->nblob);
+                p->bt_ok = true;
+            }
+            make_guard(false);
+            marks->guard = std::move(p->guard);
+            marks->kblob = std::move(p->kblob);
+            p->guard = GuardTables();
+            p->kblob.clear();
+            p->find_marks = std::move(marks);
         } else {
             // TRRE_TRACE=1: the stages of the NFT compile on stderr as they start (to find the one a pattern is slow in)
             auto trace = [&](const char* what) { if (switches().trace) fprintf(stderr, "compile: %s\n", what); };
@@ -1880,6 +1916,7 @@ int trre_compile_mode(const uint8_t* pattern, size_t len, int engine, int mode, 
 
 void trre_free(trre_prog* p) {
     if (!p) return;
+    trre_free(p->find_marks.release());
     int cur = 0;
     const bool have_cur = hipGetDevice(&cur) == hipSuccess;
     for (auto& kv : p->dev) {
@@ -1952,6 +1989,9 @@ size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap) { re
 
 size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap) {
     if (!p) return 0;
+    if (which == 5 || which == 6)                                     // (find mode: the texts / the marks forward tables; the backward DFA, 0, is one)
+        return p->find_marks ? export_blob(which == 5 ? p->gblob : p->find_marks->gblob, buf, cap) : 0;
+    if (which == 3 && p->find_marks) return export_blob(p->find_marks->kblob, buf, cap);     // (find mode: the guard goes with the scan that runs first)
     if (which == 4) return export_blob(p->gt.accept, buf, cap);       // (match mode: a byte per backward state, 1: a line that starts with the symbol is accepted)
     return export_blob(which == 0 ? p->rblob : (which == 2 ? p->nblob : (which == 3 ? p->kblob : p->gblob)), buf, cap);   // (2: the enumeration's / the backtracking fallback's tables, 3: the stack guard's)
 }
@@ -2016,6 +2056,7 @@ static int current_state(trre_prog* p, DeviceState** st) {
 int trre_scan_enqueue(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, void* stream) {
     g_scan_flags = 0;
     if (!p || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_FIND) return fail(TRRE_E_ARG, kFindOnlyMsg);
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     DeviceState* st;
     int rc = current_state(p, &st);
@@ -2165,6 +2206,7 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
                      void* stream) {
     g_scan_flags = 0;
     if (!p || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_FIND) return fail_empty(out_len, TRRE_E_ARG, kFindOnlyMsg);
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     DeviceState* st;
     int rc = current_state(p, &st);
@@ -2286,6 +2328,7 @@ int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const 
     g_scan_flags = 0;
     if (out_len) *out_len = 0;
     if (!p || !d_off || !d_out_off || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_FIND) return fail(TRRE_E_ARG, kFindOnlyMsg);
     if (p->mode != TRRE_MODE_SCAN)
         return fail(TRRE_E_UNSUPPORTED, "error: records are offered in scan mode only (a line of -m, -a, -ma prints zero or many newlines)");
     if (p->prints_newline)
@@ -2386,6 +2429,7 @@ int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     g_scan_flags = 0;
     if (out_len) *out_len = 0;
     if (!p || !d_off || !d_out_off || (n && !d_in) || (cap && !d_out)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_FIND) return fail(TRRE_E_ARG, kFindOnlyMsg);
     if (p->mode != TRRE_MODE_SCAN)
         return fail(TRRE_E_UNSUPPORTED, "error: strings are offered in scan mode only (a line of -m, -a, -ma prints zero or many newlines)");
     if (p->prints_newline)
@@ -2540,6 +2584,164 @@ int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
     return match_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_matched, out_len,
                     static_cast<hipStream_t>(stream));
+}
+
+// ---- found strings (records_block.hpp) -------------------------------------------------------------------------------------
+// One scan of the staged text under a find program's table into a buffer of the library, which grows on the size a scan reports: a
+// scan that does not fit says how much it needs and runs once more.  (The staged text is the outer context's; the scan's own
+// workspace — symbols, lane counts, status — is that of the program that runs.)
+static int find_scan(trre_prog* p, DeviceState* st, const uint8_t* d_text, size_t total, DevBuf<uint8_t>& framed, size_t* m, hipStream_t s) {
+    ScanCtx* cx = &st->ctx;
+    HIP_TRY(framed.reserve(total + 64, total + 64));
+    for (int round = 0;; ++round) {
+        int rc = enqueue(p, st, cx, TRRE_KERNEL_GUIDED_GEN, d_text, total, framed, framed.cap - 64, s);
+        if (rc) { cx->pend = Pending(); return rc; }
+        rc = finish(p, st, cx, m);
+        if (rc != TRRE_E_CAPACITY || round) return rc == TRRE_E_CAPACITY ? fail(TRRE_E_DEVICE, "error: a scan outgrew the size it reported (internal)") : rc;
+        HIP_TRY(framed.reserve(*m + 64, *m + 64));
+    }
+}
+
+// d_rec as for the strings call, of the outer program's context, which also holds the staged text (d_snap), the list offsets while
+// they are being made (d_find_off), the marks unframed (d_find_marks) and the framed texts (d_framed); the inner program's context
+// holds the framed marks (its d_framed)
+static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec,
+                   uint8_t* d_out, size_t cap, int64_t* d_match_off, size_t match_cap, int64_t* d_list_off, size_t* n_matches,
+                   size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    const int64_t T = str_tile_bytes();
+    const int64_t total = (int64_t)(n + nrec);                     // the staged text
+    const int64_t tiles = (total + T - 1) / T;
+    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
+    // 1. the offsets, on the device: nothing is written before they pass
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
+    const int bad = rec_status(cx, s, nullptr, nullptr);
+    if (bad < 0) return TRRE_E_DEVICE;
+    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
+        if (d_match_off) HIP_TRY(hipMemsetAsync(d_match_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 2. the staged text and the strings' ranks, as for the strings call — the ranks into the library's own array: the caller's
+    // are not written before the strings have passed (3)
+    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
+    HIP_TRY(cx->d_find_off.reserve(nrec + 1, (nrec + 1) * 8));
+    int64_t* loff = cx->d_find_off;
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    StrArgs sa{};
+    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
+    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = loff;
+    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
+    launch_str_part(0, sa, part, tiles, s);
+    launch_str_stage(sa, tiles, s);
+    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    launch_str_rank(sa, s);
+    // 3. a string that holds a '\n' would be several lines: the staged newlines are the strings' closing ones exactly when they are nrec
+    uint64_t staged_nl = 0;
+    if (rec_status(cx, s, const_cast<uint64_t*>(sa.base) + tiles, &staged_nl) < 0) return TRRE_E_DEVICE;
+    if (staged_nl != nrec) return fail(TRRE_E_ARG, "error: a string holds a newline: it would be several lines, each with matches of its own");
+    // 4. the marks scan, and its unframing by the strings call's passes: string i's marks end just past framed newline number i + 1,
+    // and the unframed offsets are the list offsets
+    size_t mm = 0;
+    int rc = find_scan(p->find_marks.get(), stm, cx->d_snap, (size_t)total, stm->ctx.d_framed, &mm, s);
+    if (rc) return rc;                                      // (TRRE_E_DIVERGES: *out_len stays 0)
+    if (mm < nrec) return fail(TRRE_E_DEVICE, "error: the list offsets do not add up (internal)");
+    const uint8_t* marks = stm->ctx.d_framed;
+    const size_t found = mm - nrec;
+    const int64_t RT = rec_tile_bytes();
+    const int64_t otiles = ((int64_t)mm + RT - 1) / RT, mtiles = ((int64_t)mm + T - 1) / T;
+    HIP_TRY(rec_room(cx, std::max(otiles, mtiles)));
+    HIP_TRY(cx->d_find_marks.reserve(found + 64, found + 64));
+    RecArgs oa{};
+    oa.in_v0 = marks; oa.vbeg = 0; oa.vend = (int64_t)mm; oa.nrec = (int64_t)nrec; oa.out_off = loff;
+    rec_carve(cx, otiles, oa);
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_count(oa, otiles, s);
+    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
+    launch_rec_part(1, oa, otiles, s);
+    launch_rec_locate(oa, otiles, d_bad, s);
+    uint64_t last[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&last[1], oa.base + otiles, 8, hipMemcpyDeviceToHost, s));
+    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(loff + nrec), &last[0]);
+    if (lost < 0) return TRRE_E_DEVICE;
+    if (lost || last[0] != mm || last[1] != nrec) return fail(TRRE_E_DEVICE, "error: the list offsets do not add up (internal)");
+    StrArgs ma{};
+    ma.src_v0 = marks; ma.total = (int64_t)mm; ma.dst = cx->d_find_marks; ma.dst_len = (int64_t)found;
+    ma.nrec = (int64_t)nrec; ma.out_off = loff;
+    part = reinterpret_cast<int64_t*>(cx->d_rec + 1);       // (d_rec may have grown)
+    ma.part = part;
+    launch_str_part(1, ma, part, mtiles, s);
+    launch_str_unframe(ma, mtiles, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d_list_off, loff, (nrec + 1) * 8, hipMemcpyDeviceToDevice, s));
+    // 5. the texts scan: every match's output and a '\n' — as many as there are marks
+    size_t m = 0;
+    rc = find_scan(p, st, cx->d_snap, (size_t)total, cx->d_framed, &m, s);
+    if (rc) return rc;
+    const int64_t utiles = ((int64_t)m + T - 1) / T;
+    uint64_t closed = 0;
+    RecArgs ca{};
+    if (m) {
+        HIP_TRY(rec_room(cx, utiles));
+        ca.in_v0 = cx->d_framed; ca.vbeg = 0; ca.vend = (int64_t)m;
+        rec_carve(cx, utiles, ca);
+        launch_match_count(ca, utiles, s);
+        launch_chunk_scan(ca.cnt, const_cast<uint64_t*>(ca.base), utiles, s);
+        HIP_TRY(hipGetLastError());
+        if (rec_status(cx, s, const_cast<uint64_t*>(ca.base) + utiles, &closed) < 0) return TRRE_E_DEVICE;
+    } else {
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (closed != found || m < found) return fail(TRRE_E_DEVICE, "error: the two scans of the strings disagree on the number of matches (internal)");
+    if (n_matches) *n_matches = found;
+    if (out_len) *out_len = m - found;
+    if (m - found > cap || found > match_cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    // 6. the framed texts without their newlines into the caller's buffer, and where each match starts
+    if (found == 0) {
+        if (d_match_off) HIP_TRY(hipMemsetAsync(d_match_off, 0, 8, s));
+    } else {
+        StrArgs ua{};
+        ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - found);
+        ua.nrec = (int64_t)found; ua.out_off = d_match_off;
+        ua.part = reinterpret_cast<const int64_t*>(ca.base);
+        launch_find_unframe(ua, utiles, s);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return TRRE_OK;
+}
+
+int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                             int64_t* d_match_off, size_t match_cap, int64_t* d_list_off, size_t* n_matches, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_matches) *n_matches = 0;
+    if (!p || !d_off || !d_list_off || (n && !d_in) || (cap && !d_out) || (match_cap && !d_match_off)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_FIND || !p->find_marks) return fail(TRRE_E_ARG, "error: found strings take a program compiled with TRRE_MODE_FIND");
+    if (p->prints_newline)
+        return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: the matches' outputs could not be told apart");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: find mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || match_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
+    const size_t ob = (nrec + 1) * 8, mb = d_match_off ? (match_cap + 1) * 8 : 0;
+    if (ranges_overlap(d_off, ob, d_list_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
+        ranges_overlap(d_list_off, ob, d_in, n) || ranges_overlap(d_list_off, ob, d_out, cap) || ranges_overlap(d_match_off, mb, d_in, n) ||
+        ranges_overlap(d_match_off, mb, d_out, cap) || ranges_overlap(d_match_off, mb, d_off, ob) || ranges_overlap(d_match_off, mb, d_list_off, ob))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    DeviceState *st, *stm;
+    int rc = current_state(p, &st);
+    if (!rc) rc = current_state(p->find_marks.get(), &stm);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);              // (the inner program is reached through this call only: the outer lock covers it)
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return find_on(p, st, stm, d_in, n, d_off, nrec, d_out, cap, d_match_off, match_cap, d_list_off, n_matches, out_len, static_cast<hipStream_t>(stream));
 }
 
 namespace {
@@ -2825,6 +3027,7 @@ static int host_overlap(const uint8_t* in, size_t n, const uint8_t* out, size_t 
 int trre_scan_host(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len, int device) {
     g_scan_flags = 0;
     if (!p || (n && !in) || (cap && !out)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_FIND) return fail_empty(out_len, TRRE_E_ARG, kFindOnlyMsg);
     if (out_len) *out_len = 0;
     if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     if (n == 0) return TRRE_OK;
@@ -2928,6 +3131,7 @@ int scan_shards(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* o
 int trre_scan_host_multi(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len, uint32_t device_mask) {
     g_scan_flags = 0;
     if (!p || (n && !in) || (cap && !out)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_FIND) return fail_empty(out_len, TRRE_E_ARG, kFindOnlyMsg);
     if (out_len) *out_len = 0;
     if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     int n_dev = 0;

@@ -1754,6 +1754,37 @@ __global__ __launch_bounds__(SG::THREADS) void k_match_unframe(StrArgs a) {
     str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
 }
 
+// ---- found strings (records_block.hpp; runtime.cpp: trre_find_device_strings) ----------------------------------------------
+static_assert(SG::THREADS % kWave == 0 && SG::NVEC % 4 == 0, "find_offset_vecs: a wave takes 64-byte pieces of the tile");
+
+// k_match_unframe, and the matches' offsets: a.part holds the '\n' before every tile — the matches closed before it —, a.out_off
+// is match_off and a.nrec the number of matches.  The tile's bytes and marks are staged into LDS by all threads; the barriers
+// of the compaction stand between that and every read here (pv is complete behind the second one).
+__global__ __launch_bounds__(SG::THREADS) void k_find_unframe(StrArgs a) {
+    __shared__ U128 lds[SG::NVEC + 2];
+    __shared__ uint32_t bits32[SG::NVEC / 2];
+    __shared__ uint32_t pv[SG::NVEC + 1];
+    __shared__ uint16_t inv[SG::NVEC + 2];
+    __shared__ uint32_t pre[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const StrTile<SG> t(a, blockIdx.x, false);
+    U128 w[SG::VECS + 1];
+    str_load_vecs<SG>(a, t, tid, w);
+    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
+    match_mark_vecs<SG>(t, tid, w, bits16);
+    str_keep_vecs<SG>(t, tid, w, lds);
+    __syncthreads();
+    const uint32_t marks = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
+    str_fill_pv<SG>(bits16, pre[tid], tid, pv);
+    __syncthreads();
+    find_offset_vecs<SG>(a, t, tid, bits16, pv);
+    const StrOut<SG> o(a, t, marks);
+    str_fill_inv<SG>(t, o, tid, bits16, pv, inv);
+    __syncthreads();
+    str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
+}
+
 void launch_match_verdict(int sym_bits, const MatchArgs& a, void* stream) {
     const int64_t groups = (a.nrec + kMatchThreads - 1) / kMatchThreads;
     const dim3 grid((unsigned)(groups < 1 ? 1 : groups > 256 * 16 ? 256 * 16 : groups)), block(kMatchThreads);
@@ -1773,6 +1804,9 @@ void launch_match_count(const RecArgs& a, int64_t tiles, void* stream) {
 }
 void launch_match_unframe(const StrArgs& a, int64_t tiles, void* stream) {
     hipLaunchKernelGGL(k_match_unframe, dim3((unsigned)tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_find_unframe(const StrArgs& a, int64_t tiles, void* stream) {
+    hipLaunchKernelGGL(k_find_unframe, dim3((unsigned)tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
 }
 
 int64_t rec_tile_bytes() { return RG::TILE; }
