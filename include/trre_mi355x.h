@@ -53,6 +53,10 @@ extern "C" {
 #define TRRE_MODE_FIND 4 /* every match of every string, the rest thrown away (findall, grep -o): the outputs of the scan loop's
                           * successful attempts (trre_nft.c:775-790) as a list per string.  NFT engine only; runs through
                           * trre_find_device_strings and nothing else */
+#define TRRE_MODE_SPANS 8 /* where every match of every string starts and ends (finditer().span(), str.find, str.count): the positions
+                           * of the same attempts, nothing of what they print.  NFT engine only; runs through
+                           * trre_span_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and stay
+                           * TRRE_E_ARG, as they were) */
 
 /* return codes */
 #define TRRE_OK 0
@@ -142,7 +146,7 @@ int trre_set_kernel(trre_prog* p, int kernel_family); /* force a family (benchma
  * tests).  Returns the blob size; copies min(size, cap) bytes. */
 size_t trre_export_tables(const trre_prog* p, void* buf, size_t cap);
 size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap); /* 0 if the pattern does not fold */
-size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted, 5 / 6 (find mode) the texts / the marks forward tables, both over the backward DFA of 0; 0 if none */
+size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted, 5 / 6 (find mode) the texts / the marks forward tables, both over the backward DFA of 0, 7 (spans mode) the markers' forward table, over the backward DFA of 0; 0 if none */
 
 /* Replaces the scan branch of main() (trre_nft.c:775-790 / trre_dft.c:1272-1286)
  * for a whole buffer that is already resident in HBM.
@@ -284,6 +288,42 @@ int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
  * the strings call. */
 int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
                              int64_t* d_match_off, size_t match_cap, int64_t* d_list_off, size_t* n_matches, size_t* out_len, void* stream);
+
+/* Match spans: the same column of strings under a program compiled with TRRE_MODE_SPANS — WHERE every match of every string
+ * starts and ends (re.finditer().span(), str.find, str.count, str.contains, the boundaries for splitting a column).  The
+ * attempts are those of trre_find_device_strings: for a string s that holds no '\n', L is s cut at its first NUL; the scan
+ * loop (trre_nft.c:775-790) runs an attempt at position 0 of L; an attempt that reaches FINAL after consuming k bytes from
+ * position p is the match (p, p + k); if k > 0 the next attempt starts at p + k, otherwise one raw byte is skipped; one more
+ * attempt runs on the empty tail.  Empty matches count ('x*' on "bb": (0,0) (1,1) (2,2)); a NUL ends the search ('(cat|dog)'
+ * on "a cat\0dog": (2,5) alone).  What the program prints plays no part: a program that prints a '\n' of its own is served.
+ *   d_start, d_end  room for span_cap entries each: match j is d_in[d_start[j] .. d_end[j]) — byte positions in d_in, absolute,
+ *                   d_off[i] <= d_start[j] <= d_end[j] <= d_off[i + 1] for the string i that holds match j.  Two arrays, so
+ *                   that adjacent matches store adjacent words.  Both may be null with span_cap == 0
+ *   d_list_off      nrec + 1 entries: d_list_off[i] is the number of matches in strings 0 .. i - 1, d_list_off[nrec] = *n_matches
+ * *n_matches may be null.  d_in is only read; there is no output buffer.  nrec == 0 is valid with n == 0: d_list_off[0] = 0.
+ * The offsets' check (TRRE_E_ARG, nothing written), a string that holds a '\n' (TRRE_E_ARG, found on the device from the staged
+ * text's newline count before anything of the caller's is written) and a split-form scan in flight: as for
+ * trre_find_device_strings.  Any overlap among d_off, d_start, d_end, d_list_off, or of one of them with d_in: TRRE_E_ARG.
+ * Refused before the device is touched: a program not compiled with TRRE_MODE_SPANS (TRRE_E_ARG) — and a spans program given
+ * to any other scan call (TRRE_E_ARG) —; TRRE_KERNEL_BACKTRACK forced through trre_set_kernel (TRRE_E_UNSUPPORTED).  Refused by
+ * trre_compile_mode (TRRE_E_UNSUPPORTED): TRRE_ENGINE_DFT and a pattern without guided tables.  The scan runs on the general
+ * guided family (trre_info.kernel: TRRE_KERNEL_GUIDED_GEN); the stack guard applies as in scan mode.
+ *   TRRE_E_CAPACITY  exactly when there are more than span_cap matches: *n_matches holds the number needed and d_list_off is
+ *                    valid; d_start and d_end have not been written at all.  span_cap == 0 is the size query — and all that
+ *                    count and contains need.
+ *   TRRE_E_DIVERGES  *n_matches = 0; the arrays are unspecified; trre_last_error() holds the reference's message.
+ * How: ONE scan of the strings call's staged text under a forward table that prints none of the program's output: a position
+ * byte per staged byte ('\n' for a '\n'), 0x01 in front of the first byte of every match, 0x02 behind its last.  With the
+ * markers taken out the framed text is the staged text's length with its newlines in place, so for a marker at framed
+ * position q, position = q - (0x01 before q) - (0x02 before q) - ('\n' before q): 0x01 number j gives d_start[j], 0x02 number j
+ * d_end[j], and '\n' number i gives d_list_off[i + 1] = 0x01 before q.  A count pass (three counters per 16 KiB framed tile), their
+ * exclusive sums and a rank pass do that arithmetic; every word is stored once, by the lane that owns its byte.
+ * Device memory, kept by the (prog, device) until trre_free: the staged text, n + nrec + 64 bytes; the framed text, n + nrec +
+ * 2 * n_matches + 64 bytes (it grows on the size the scan reports, which costs the first call on a column with more matches
+ * one more scan); 8 (nrec + 1) bytes of the staging passes' ranks; 48 bytes per 16 KiB of the framed text; and the general
+ * guided family's workspace once.  Synchronous with respect to `stream`; trre_last_scan_flags as for the strings call. */
+int trre_span_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* d_start,
+                             int64_t* d_end, size_t span_cap, int64_t* d_list_off, size_t* n_matches, void* stream);
 
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRRE_LIB_PATH") or os.path.join(_HERE, "lib", "libtrre_mi355x.so")   # override: A/B builds only
 
 ENGINE_NFT, ENGINE_DFT = 0, 1
-MODE_SCAN, MODE_MATCH, MODE_SCAN_ALL, MODE_MATCH_ALL, MODE_FIND = 0, 1, 2, 3, 4
+MODE_SCAN, MODE_MATCH, MODE_SCAN_ALL, MODE_MATCH_ALL, MODE_FIND, MODE_SPANS = 0, 1, 2, 3, 4, 8
 _ENGINES = {"nft": ENGINE_NFT, "dft": ENGINE_DFT, ENGINE_NFT: ENGINE_NFT, ENGINE_DFT: ENGINE_DFT}
 
 KERNEL_AUTO, KERNEL_BYTEMAP, KERNEL_TILE_LP, KERNEL_TILE_GEN, KERNEL_STREAM_LP, KERNEL_STREAM_GEN = 0, 1, 2, 3, 4, 5
@@ -96,6 +96,7 @@ def lib():
         L.trre_scan_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_match_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_find_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_span_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -126,11 +127,12 @@ class Program:
     def __init__(self, pattern, engine="nft", mode="scan"):
         """mode "scan" (default), "match" (`trre -m`: whole-line matches only, NFT engine), "scan_all" (`trre -a`) or
         "match_all" (`trre -ma`): generator modes, every accepting path prints (NFT engine), or "find": every match of every
-        string as a list per string (find_strings / find_list, NFT engine)"""
+        string as a list per string (find_strings / find_list, NFT engine), or "spans": where every match of every string starts
+        and ends (span_strings / span_list / count_strings, NFT engine)"""
         self.pattern = _bytes(pattern)
         self.engine = _ENGINES[engine]
         self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL,
-                     "find": MODE_FIND}.get(mode, mode)
+                     "find": MODE_FIND, "spans": MODE_SPANS}.get(mode, mode)
         self._h = ctypes.c_void_p()
         _check(lib().trre_compile_mode(self.pattern, len(self.pattern), self.engine, self.mode, ctypes.byref(self._h)))
 
@@ -190,6 +192,18 @@ class Program:
             blobs.append(buf.raw[:n])
         if not blobs[1]:
             return (b"", b"", b"")
+        return tuple(blobs)
+
+    def export_span_tables(self):
+        """spans mode: (backward DFA blob, the markers' forward tables blob), or (b"", b"")"""
+        blobs = []
+        for which in (0, 7):
+            n = lib().trre_export_guided_tables(self._h, which, None, 0)
+            buf = ctypes.create_string_buffer(max(n, 1))
+            lib().trre_export_guided_tables(self._h, which, buf, n)
+            blobs.append(buf.raw[:n])
+        if not blobs[1]:
+            return (b"", b"")
         return tuple(blobs)
 
     def export_gen_tables(self):
@@ -408,6 +422,60 @@ class Program:
         mo = match_off.cpu().numpy().tolist()
         lo = list_off.cpu().numpy().tolist()
         return [[blob[mo[j]:mo[j + 1]] for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
+
+    def _span_call(self, values, offsets, starts, ends, cap, stream):
+        """one trre_span_device_strings call: (rc, n_matches, list_offsets)"""
+        import torch
+        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
+        n, nrec = values.numel(), offsets.numel() - 1
+        list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
+        k = ctypes.c_size_t()
+        with torch.cuda.device(values.device):
+            rc = lib().trre_span_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec,
+                                                starts.data_ptr() if cap else None, ends.data_ptr() if cap else None, cap,
+                                                list_off.data_ptr(), ctypes.byref(k), s)
+        return rc, k.value, list_off
+
+    def span_strings(self, values, offsets, stream=None):
+        """Match spans (trre_span_device_strings; a program compiled with mode="spans"): values and offsets as for scan_strings,
+        no string holding a b"\\n".  Returns (starts, ends, list_offsets), int64: string i's matches are numbers list_offsets[i]
+        .. list_offsets[i + 1] - 1, and match j is values[starts[j]:ends[j]] — positions in values, absolute.  Two calls: the
+        size query, then the one that fills arrays of exactly that size."""
+        import torch
+        rc, k, list_off = self._span_call(values, offsets, None, None, 0, stream)
+        if rc not in (0, E_CAPACITY):
+            _check(rc)
+        starts = torch.empty(k, dtype=torch.int64, device=values.device)
+        ends = torch.empty(k, dtype=torch.int64, device=values.device)
+        if rc == E_CAPACITY:
+            rc, k2, list_off = self._span_call(values, offsets, starts, ends, k, stream)
+            _check(rc)
+            assert k2 == k
+        return starts, ends, list_off
+
+    def count_strings(self, values, offsets, stream=None):
+        """matches per string (str.count; > 0: str.contains), int64 — the size query alone: no span is stored"""
+        rc, _, list_off = self._span_call(values, offsets, None, None, 0, stream)
+        if rc not in (0, E_CAPACITY):
+            _check(rc)
+        return list_off[1:] - list_off[:-1]
+
+    def span_list(self, records, device=0):
+        """list of bytes in -> per string a list of (start, end) relative to that string, as m.span() of re.finditer (through
+        span_strings)"""
+        import numpy as np
+        import torch
+        recs = [_bytes(r) for r in records]
+        off = np.zeros(len(recs) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in recs], out=off[1:])
+        dev = torch.device("cuda", device)
+        packed = b"".join(recs)
+        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
+        starts, ends, list_off = self.span_strings(values, torch.from_numpy(off).to(dev))
+        st, en, lo = starts.cpu().numpy().tolist(), ends.cpu().numpy().tolist(), list_off.cpu().numpy().tolist()
+        return [[(st[j] - int(off[i]), en[j] - int(off[i])) for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
 
     @staticmethod
     def _map_list(records, device, scan):

@@ -412,6 +412,14 @@ GuidedTables build_guided_nft(const NftNodes& nodes, const GuidedLimits& lim = G
 //           the scan of a text is, line by line, as many bytes as the line has matches
 // Both or neither (false: beyond the limits); texts.sym_bits == marks.sym_bits, so the backward blob is one.
 bool build_guided_find(const NftNodes& nodes, GuidedTables& texts, GuidedTables& marks, const GuidedLimits& lim = GuidedLimits());
+// Spans mode (TRRE_MODE_SPANS; nodes as for scan mode): ONE forward table, a third variant of the find walk that prints nothing
+// of the program's own.  Every input byte prints one position byte ('.'; the line's '\n' prints '\n'), the cell that starts a
+// successful attempt prints kSpanA in front of it, every FINAL prints kSpanB: the scan of a text, its markers taken out, has the
+// text's length and its newlines where the text has them, so a marker's place among the position bytes is a position in the
+// text.  A NUL prints its '.', and the bytes behind it print theirs from a forward state of their own (SKIP itself stays silent:
+// the lanes of the general families walk the rest of a line that is not theirs in it).  !ok: beyond the limits.
+constexpr uint8_t kSpanA = 0x01, kSpanB = 0x02, kSpanDot = '.';
+GuidedTables build_guided_spans(const NftNodes& nodes, const GuidedLimits& lim = GuidedLimits());
 // The deterministic engine in the same form (trre_dft.c:1110-1196): the backward DFA says at every position what becomes of an
 // attempt from START there (and which class the byte has), the forward transducer walks the determinised tables only through
 // attempts that succeed.  For patterns whose scan loop does not fold into a stream table (a loop before the decision:

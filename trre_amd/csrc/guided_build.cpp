@@ -115,6 +115,19 @@ public:
         texts = std::move(g);
     }
 
+    // spans mode (front.hpp: build_guided_spans): scan mode's backward DFA under span_cell's forward table
+    GuidedTables run_spans() {
+        GuidedTables g;
+        byte_classes(g);
+        backward(g);
+        find_ = kFindSpans;
+        forward(g);
+        g.wide = g.n_rev > 256;
+        g.sym_bits = g.wide ? 16 : ((g.n_rev <= 16 && g.fwd.g16_ok) ? 4 : 8);
+        g.ok = true;
+        return g;
+    }
+
 private:
     // match mode: which symbols at a line's first byte mean "accepted" — the root cell's own question (match_cell, s == 0): does
     // the start list hold an entry the search does not get past.  (An entry that diverges counts: such a line never reaches the
@@ -205,8 +218,8 @@ private:
     uint64_t work_ = 0;
 
     // forward states: 0 root, 1 SKIP, 2 DONE (the stream kernels' conventions), then (node, muted)
-    uint32_t intern_fwd(uint32_t node, bool muted) {
-        const uint64_t key = (uint64_t)node * 2 + (muted ? 1 : 0);
+    uint32_t intern_fwd(uint32_t node, bool muted) { return intern_key((uint64_t)node * 2 + (muted ? 1 : 0)); }
+    uint32_t intern_key(uint64_t key) {
         auto hit = fwd_index_.find(key);
         if (hit != fwd_index_.end()) return hit->second;
         if (fwd_.size() >= lim_.max_fwd_states) throw StreamGiveUp();
@@ -223,6 +236,7 @@ private:
         const RevSets& r = rev_[y];
         const bool at_end = y == kSymEol || y == kSymNul;
         if (match_) return match_cell(s, y, r, at_end);
+        if (find_ == kFindSpans) return span_cell(s, y, r, at_end);
         if (find_) return find_cell(s, y, r, at_end);
         const std::vector<NodeFollow>& start = nd_.follow[n_nodes_];
         bool fresh = s == 0;
@@ -363,6 +377,65 @@ private:
         return c;
     }
 
+    // Spans mode (trre_span_device_strings): find_cell's walk, the same next, eol and diverging cells, and nothing of the program's
+    // own output.  A cell prints, in the order things happen at its byte: kSpanB for every FINAL; kSpanA when an attempt that will
+    // succeed starts here (fresh, an entry the search does not get past, not diverging) — in front of the byte's own position
+    // byte, so that an attempt which consumed nothing prints A B —; then one position byte: '.' for a byte inside the line, raw or
+    // consumed, and for a NUL, '\n' for the line's '\n'.  At most B A B and the position byte: four bytes, the 16-byte entries'
+    // fast form.  A NUL ends the line's attempts but not its position bytes: its cell hands over to a forward state of this
+    // table's own (kAfterNul, not a node) that prints '.' per byte up to the '\n', which prints '\n' and ends the line.  SKIP
+    // (s == 1) stays silent as in every table: a lane of the general families that starts inside a line walks the rest of that
+    // line, which is another lane's, in SKIP.  No cell is muted: mute is about the output, which is not printed.
+    static constexpr uint64_t kAfterNul = ~0ull;
+    StreamCell span_cell(uint32_t s, uint32_t y, const RevSets& r, bool at_end) {
+        StreamCell c;
+        if (s >= 3 && fwd_[s] == kAfterNul) {
+            c.out.push_back(y == kSymEol ? '\n' : (char)kSpanDot);
+            c.next = y == kSymEol ? 0u : s;
+            c.eol = y == kSymEol;
+            return c;
+        }
+        const std::vector<NodeFollow>& start = nd_.follow[n_nodes_];
+        bool fresh = s == 0;
+        const std::vector<NodeFollow>* cur = fresh ? &start : &nd_.follow[fwd_[s] / 2];
+        bool ended = false;
+        for (;;) {
+            const int e = decisive(*cur, r, true);
+            if (e < 0) {
+                if (!fresh) { c.diverge = true; c.next = 1; c.out.clear(); return c; }     // cannot happen (cell())
+                if (at_end) { ended = true; break; }
+                c.out.push_back((char)kSpanDot);     // no match here: the raw byte
+                c.next = 0;
+                break;
+            }
+            const NodeFollow& f = (*cur)[e];
+            if (diverges(f, r)) { c.diverge = true; c.next = 2; return c; }
+            if (fresh) c.out.push_back((char)kSpanA);
+            if (f.target == kNodeFinal) {
+                c.out.push_back((char)kSpanB);
+                if (fresh) {         // an attempt that consumed nothing
+                    if (at_end) { ended = true; break; }
+                    c.out.push_back((char)kSpanDot);     // ... inside the line: the raw byte behind it
+                    c.next = 0;
+                    break;
+                }
+                fresh = true;
+                cur = &start;
+                continue;
+            }
+            c.out.push_back((char)kSpanDot);         // this byte is consumed by node f.target
+            c.next = intern_fwd(f.target, false);
+            break;
+        }
+        if (ended) {
+            c.out.push_back(y == kSymNul ? (char)kSpanDot : '\n');
+            c.next = y == kSymNul ? intern_key(kAfterNul) : 0u;
+            c.eol = y == kSymEol;
+        }
+        if (c.out.size() > lim_.max_out) throw StreamGiveUp();
+        return c;
+    }
+
     void forward(GuidedTables& g) {
         StreamPackInput in;
         fwd_.assign(3, 0);
@@ -382,8 +455,8 @@ private:
     GuidedLimits lim_;
     uint32_t n_nodes_;
     bool match_;
-    enum : int { kFindTexts = 1, kFindMarks = 2 };
-    int find_ = 0;                                  // 0: scan / match mode (cell, match_cell); else which table find_cell builds
+    enum : int { kFindTexts = 1, kFindMarks = 2, kFindSpans = 3 };
+    int find_ = 0;                                  // 0: scan / match mode (cell, match_cell); else which table find_cell / span_cell builds
     std::vector<int> rep_;                          // class -> a representative byte
     std::vector<std::vector<uint32_t>> readers_;    // class -> nodes that read its bytes
     std::vector<RevSets> rev_;
@@ -672,6 +745,14 @@ bool build_guided_find(const NftNodes& nodes, GuidedTables& texts, GuidedTables&
     } catch (const StreamGiveUp&) {
         texts = marks = GuidedTables();
         return false;
+    }
+}
+
+GuidedTables build_guided_spans(const NftNodes& nodes, const GuidedLimits& lim) {
+    try {
+        return GuidedBuilder(nodes, lim).run_spans();
+    } catch (const StreamGiveUp&) {
+        return GuidedTables();
     }
 }
 

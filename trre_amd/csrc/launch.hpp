@@ -14,6 +14,7 @@ struct MapGenArgs;
 struct RecArgs;
 struct StrArgs;
 struct MatchArgs;
+struct SpanArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -107,6 +108,10 @@ void launch_match_unframe(const StrArgs& a, int64_t tiles, void* stream);
 // found strings (records_block.hpp): launch_match_unframe's compaction and the matches' offsets (a.part: the '\n' before every tile,
 // a.out_off: match_off, a.nrec: the number of matches)
 void launch_find_unframe(const StrArgs& a, int64_t tiles, void* stream);
+// match spans (records_block.hpp): the markers per framed tile (a.cnt), then — behind the three exclusive scans — the spans and
+// the list offsets (a.tiles tiles each)
+void launch_span_count(const SpanArgs& a, void* stream);
+void launch_span_emit(const SpanArgs& a, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

@@ -624,4 +624,120 @@ TRRE_HD void find_offset_vecs(const StrArgs& a, const StrTile<G>& t, int tid, co
     }
 }
 
+// ---- match spans (trre_span_device_strings) --------------------------------------------------------------------------------
+// A spans-mode program says WHERE the scan loop's successful attempts start and end.  ONE scan of the strings call's staged
+// text under the forward table of guided_build.cpp: span_cell gives the framed text: per staged byte one position byte ('\n'
+// for a '\n'), A = 0x01 in front of the first position byte of every match, B = 0x02 behind its last.  With A and B taken out
+// the framed text is the staged text, byte for byte in length and newlines; string i's bytes sit at off[i] + i in the staged
+// text.  So with a, b, l the A, B, '\n' before framed position q:
+//     A number j at q      start[j] = q - a - b - l         (a = j)
+//     B number j at q      end[j]   = q - a - b - l         (b = j, a = j + 1)
+//     '\n' number i at q   list_off[i + 1] = a              (l = i)
+// positions in the caller's d_in, absolute.  The passes:
+//   k_span_count  A, B, '\n' per framed tile: cnt[3][tiles];  k_chunk_scan, three times: base[3][tiles + 1]; the totals are
+//                 read back and checked (#A = #B, #'\n' = nrec, framed length = staged length + 2 #A) before anything is stored
+//   k_span_emit   the tile's marks (a bit per byte and kind, from the thread's own vectors) into LDS; a workgroup scan of the
+//                 marks per thread segment (A and B share a word: a tile holds fewer than 65 536 bytes); then a wave takes 64
+//                 framed bytes at a time: the three 64-bit words of a piece are what three ballots would give, read from the
+//                 mark images; a lane's ranks are tile base + marks before the piece + set bits below the lane
+// Who writes which word: list_off[0] thread 0 of tile 0; every other word the lane that owns its marker byte, once; adjacent
+// ranks are stored by adjacent marker lanes.  lists_only: start and end are not stored at all (TRRE_E_CAPACITY, the size query).
+struct SpanArgs {
+    const uint8_t* src;     // the framed text: 16-byte aligned, whole vectors readable behind its end
+    int64_t total;          // framed length
+    int64_t* start;         // [n_match]
+    int64_t* end;           // [n_match]
+    int64_t* list_off;      // [nrec + 1]
+    int64_t n_match, nrec;
+    int64_t tiles;
+    uint64_t* cnt;          // [3][tiles] A, B, '\n' per tile
+    const uint64_t* base;   // [3][tiles + 1] their exclusive scans
+    uint32_t lists_only;
+};
+constexpr uint32_t kSpanA4 = 0x01010101u, kSpanB4 = 0x02020202u, kSpanNl4 = 0x0a0a0a0au;
+
+// 4-bit mask of the bytes of w equal to the byte c4 repeats (rec_nl4's exact zero-byte test)
+TRRE_HD uint32_t span_eq4(uint32_t w, uint32_t c4) {
+    const uint32_t x = w ^ c4;
+    const uint32_t z = ~((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x)) & 0x80808080u;
+    return (((z >> 7) * 0x00204081u) >> 21) & 0xfu;
+}
+TRRE_HD uint32_t span_eq16(const U128& w, uint32_t c4) {
+    return span_eq4(w.x, c4) | span_eq4(w.y, c4) << 4 | span_eq4(w.z, c4) << 8 | span_eq4(w.w, c4) << 12;
+}
+// the marks of the thread's vectors of tile b (vector q = j * THREADS + tid: coalesced), valid bytes only; c[0..2] += the
+// thread's A, B, '\n'.  bits: [3][NVEC] 16-bit masks, or null (k_span_count)
+template <class G>
+TRRE_HD void span_mark_vecs(const SpanArgs& a, int64_t b, int tid, uint16_t* bits, uint32_t (&c)[3]) {
+    U128 w[G::VECS];
+    for (int j = 0; j < G::VECS; ++j) {
+        const int64_t v = b * G::TILE + 16 * ((int64_t)j * G::THREADS + tid);
+        if (v < a.total) w[j] = rec_load16(a.src + v);
+    }
+    for (int j = 0; j < G::VECS; ++j) {
+        const int q = j * G::THREADS + tid;
+        const int64_t v = b * G::TILE + 16 * (int64_t)q;
+        uint32_t m[3] = {0u, 0u, 0u};
+        if (v < a.total) {
+            const uint32_t ok = rec_valid16(v, 0, a.total);
+            m[0] = span_eq16(w[j], kSpanA4) & ok; m[1] = span_eq16(w[j], kSpanB4) & ok; m[2] = span_eq16(w[j], kSpanNl4) & ok;
+        }
+        for (int x = 0; x < 3; ++x) {
+            if (bits) bits[x * G::NVEC + q] = (uint16_t)m[x];
+            c[x] += rec_popc(m[x]);
+        }
+    }
+}
+// marks in the thread's rank segment, vectors [tid * VECS, tid * VECS + VECS): A | B << 16, and '\n'
+template <class G>
+TRRE_HD void span_seg_count(const uint16_t* bits, int tid, uint32_t& ab, uint32_t& nl) {
+    static_assert(G::TILE < 65536, "A and B counts of a tile share a 32-bit word");
+    ab = nl = 0;
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        ab += rec_popc(bits[q]) | rec_popc(bits[G::NVEC + q]) << 16;
+        nl += rec_popc(bits[2 * G::NVEC + q]);
+    }
+}
+// marks before each of the thread's segment vectors (pre_ab, pre_nl: before the segment)
+template <class G>
+TRRE_HD void span_fill_pv(const uint16_t* bits, uint32_t pre_ab, uint32_t pre_nl, int tid, uint32_t* pv_ab, uint32_t* pv_nl) {
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        pv_ab[q] = pre_ab; pv_nl[q] = pre_nl;
+        pre_ab += rec_popc(bits[q]) | rec_popc(bits[G::NVEC + q]) << 16;
+        pre_nl += rec_popc(bits[2 * G::NVEC + q]);
+    }
+}
+TRRE_HD uint64_t span_word(const uint16_t* bits16, int k) {
+    return (uint64_t)bits16[4 * k] | (uint64_t)bits16[4 * k + 1] << 16 | (uint64_t)bits16[4 * k + 2] << 32 | (uint64_t)bits16[4 * k + 3] << 48;
+}
+// k_span_emit, behind the barrier that completes bits and pv: the words of the tile's markers
+template <class G>
+TRRE_HD void span_emit_pieces(const SpanArgs& a, int64_t b, int tid, const uint16_t* bits, const uint32_t* pv_ab, const uint32_t* pv_nl) {
+    static_assert(G::THREADS % 64 == 0 && G::NVEC % 4 == 0, "a wave takes 64-byte pieces of the tile");
+    constexpr int kPieces = G::NVEC / 4, kWaves = G::THREADS / 64;
+    const int lane = tid & 63;
+    const int64_t s0 = b * G::TILE;
+    const int64_t a0 = (int64_t)a.base[b], b0 = (int64_t)a.base[a.tiles + 1 + b], l0 = (int64_t)a.base[2 * (a.tiles + 1) + b];
+    if (b == 0 && tid == 0) a.list_off[0] = 0;
+    for (int k = tid >> 6; k < kPieces; k += kWaves) {
+        const uint64_t wa = span_word(bits, k), wb = span_word(bits + G::NVEC, k), wl = span_word(bits + 2 * G::NVEC, k);
+        if (!(((wa | wb | wl) >> lane) & 1u)) continue;
+        const uint64_t below = (1ull << lane) - 1ull;
+        const int64_t na = a0 + (int64_t)(pv_ab[4 * k] & 0xffffu) + (int64_t)match_popc64(wa & below);
+        const int64_t nb = b0 + (int64_t)(pv_ab[4 * k] >> 16) + (int64_t)match_popc64(wb & below);
+        const int64_t nl = l0 + (int64_t)pv_nl[4 * k] + (int64_t)match_popc64(wl & below);
+        const int64_t pos = s0 + 64 * (int64_t)k + lane - na - nb - nl;
+        // (never beyond: the three totals were checked against n_match and nrec before this pass)
+        if ((wa >> lane) & 1u) {
+            if (!a.lists_only && na < a.n_match) a.start[na] = pos;
+        } else if ((wb >> lane) & 1u) {
+            if (!a.lists_only && nb < a.n_match) a.end[nb] = pos;
+        } else if (nl < a.nrec) {
+            a.list_off[nl + 1] = na;
+        }
+    }
+}
+
 }  // namespace trre

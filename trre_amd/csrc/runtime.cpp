@@ -521,6 +521,7 @@ int general_family(const trre_prog& p, bool stream_ok) {
 int auto_family(const trre_prog& p) {
     using namespace trre;
     if (p.mode == TRRE_MODE_FIND) return TRRE_KERNEL_GUIDED_GEN;      // (both scans of trre_find_device_strings: their outputs are no one's input length)
+    if (p.mode == TRRE_MODE_SPANS) return TRRE_KERNEL_GUIDED_GEN;     // (the scan of trre_span_device_strings: the table is never length-preserving)
     if (p.lazy_only) return TRRE_KERNEL_DFT_LAZY;      // beyond the eager construction's caps: the tables grow with the input (lazy_block.hpp)
     if (p.engine == TRRE_ENGINE_DFT && (p.dt.flags & kFlagMemoryless)) return TRRE_KERNEL_BYTEMAP;
     // a stream table too large for LDS is walked through L1/L2 (<= 0.35 TB/s); guided tables with a small forward table
@@ -658,9 +659,15 @@ constexpr uint64_t kGuardBudget = 1ull << 23;              // search steps per l
 constexpr uint64_t kGuardCallBudget = 1ull << 35;
 constexpr const char* kStackMsg = "error: stack max capacity reached";
 constexpr const char* kFindOnlyMsg = "error: a program compiled with TRRE_MODE_FIND runs through trre_find_device_strings only";
+constexpr const char* kSpansOnlyMsg = "error: a program compiled with TRRE_MODE_SPANS runs through trre_span_device_strings only";
 constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
+// a program that one call alone runs: that call's name for every other call's refusal (null: any scan call may run it)
+const char* own_call_only(const trre_prog& p) {
+    return p.mode == TRRE_MODE_FIND ? kFindOnlyMsg : p.mode == TRRE_MODE_SPANS ? kSpansOnlyMsg : nullptr;
+}
 bool guard_applies(const trre_prog& p, const ScanCtx& cx, size_t n) {
-    return !trre::switches().no_stack_guard && p.guard.on && !cx.guard_off && (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH || p.mode == TRRE_MODE_FIND) && n + 1 >= p.guard.l_min;
+    return !trre::switches().no_stack_guard && p.guard.on && !cx.guard_off &&
+           (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH || p.mode == TRRE_MODE_FIND || p.mode == TRRE_MODE_SPANS) && n + 1 >= p.guard.l_min;
 }
 struct GuardHit {
     bool hit = false;
@@ -1718,7 +1725,10 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
     if (!out) return fail(TRRE_E_ARG, "error: null output handle");
     *out = nullptr;
     if (engine != TRRE_ENGINE_NFT && engine != TRRE_ENGINE_DFT) return fail(TRRE_E_ARG, "error: unknown engine");
-    if (mode != TRRE_MODE_SCAN && mode != TRRE_MODE_MATCH && mode != TRRE_MODE_FIND && !is_generate(mode)) return fail(TRRE_E_ARG, "error: unknown mode");
+    if (mode != TRRE_MODE_SCAN && mode != TRRE_MODE_MATCH && mode != TRRE_MODE_FIND && mode != TRRE_MODE_SPANS && !is_generate(mode))
+        return fail(TRRE_E_ARG, "error: unknown mode");
+    if (mode == TRRE_MODE_SPANS && engine != TRRE_ENGINE_NFT)
+        return fail(TRRE_E_UNSUPPORTED, "error: spans mode is offered for the non-deterministic engine only (the deterministic engine's matches cannot be told from its raw bytes by the reference)");
     if (mode == TRRE_MODE_FIND && engine != TRRE_ENGINE_NFT)
         return fail(TRRE_E_UNSUPPORTED, "error: find mode is offered for the non-deterministic engine only (the deterministic engine's matches cannot be told from its raw bytes by the reference)");
     if (mode == TRRE_MODE_MATCH && engine != TRRE_ENGINE_NFT)
@@ -1829,6 +1839,23 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
             p->guard = GuardTables();
             p->kblob.clear();
             p->find_marks = std::move(marks);
+        } else if (mode == TRRE_MODE_SPANS) {
+            // trre_span_device_strings: the scan loop's nodes under ONE forward table that prints markers and position bytes
+            // (guided_build.cpp: span_cell).  Nothing else can run a spans program: no other tables (the backtracking lists are
+            // kept so that trre_set_kernel can name that family and the span call can refuse it); the stack guard as in scan mode
+            const NftNodes nodes = build_nft_nodes(nft);
+            p->nft_nodes = (uint32_t)nodes.node.size();
+            p->gt = build_guided_spans(nodes);
+            if (!p->gt.ok)
+                return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, and this pattern is beyond their limits (a backward automaton of more than 16 384 states)");
+            {
+                GenTables lists;
+                lists.nodes = nodes;
+                lists.ok = true;
+                serialize_gen(lists, p->nblob);
+                p->bt_ok = true;
+            }
+            make_guard(false);
         } else {
             // TRRE_TRACE=1: the stages of the NFT compile on stderr as they start (to find the one a pattern is slow in)
             auto trace = [&](const char* what) { if (switches().trace) fprintf(stderr, "compile: %s\n", what); };
@@ -1991,6 +2018,7 @@ size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_
     if (!p) return 0;
     if (which == 5 || which == 6)                                     // (find mode: the texts / the marks forward tables; the backward DFA, 0, is one)
         return p->find_marks ? export_blob(which == 5 ? p->gblob : p->find_marks->gblob, buf, cap) : 0;
+    if (which == 7) return p->mode == TRRE_MODE_SPANS ? export_blob(p->gblob, buf, cap) : 0;     // (spans mode: the markers' forward table)
     if (which == 3 && p->find_marks) return export_blob(p->find_marks->kblob, buf, cap);     // (find mode: the guard goes with the scan that runs first)
     if (which == 4) return export_blob(p->gt.accept, buf, cap);       // (match mode: a byte per backward state, 1: a line that starts with the symbol is accepted)
     return export_blob(which == 0 ? p->rblob : (which == 2 ? p->nblob : (which == 3 ? p->kblob : p->gblob)), buf, cap);   // (2: the enumeration's / the backtracking fallback's tables, 3: the stack guard's)
@@ -2056,7 +2084,7 @@ static int current_state(trre_prog* p, DeviceState** st) {
 int trre_scan_enqueue(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, void* stream) {
     g_scan_flags = 0;
     if (!p || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode == TRRE_MODE_FIND) return fail(TRRE_E_ARG, kFindOnlyMsg);
+    if (own_call_only(*p)) return fail(TRRE_E_ARG, own_call_only(*p));
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     DeviceState* st;
     int rc = current_state(p, &st);
@@ -2206,7 +2234,7 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
                      void* stream) {
     g_scan_flags = 0;
     if (!p || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode == TRRE_MODE_FIND) return fail_empty(out_len, TRRE_E_ARG, kFindOnlyMsg);
+    if (own_call_only(*p)) return fail_empty(out_len, TRRE_E_ARG, own_call_only(*p));
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     DeviceState* st;
     int rc = current_state(p, &st);
@@ -2328,7 +2356,7 @@ int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const 
     g_scan_flags = 0;
     if (out_len) *out_len = 0;
     if (!p || !d_off || !d_out_off || (n && (!d_in || !d_out))) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode == TRRE_MODE_FIND) return fail(TRRE_E_ARG, kFindOnlyMsg);
+    if (own_call_only(*p)) return fail(TRRE_E_ARG, own_call_only(*p));
     if (p->mode != TRRE_MODE_SCAN)
         return fail(TRRE_E_UNSUPPORTED, "error: records are offered in scan mode only (a line of -m, -a, -ma prints zero or many newlines)");
     if (p->prints_newline)
@@ -2429,7 +2457,7 @@ int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     g_scan_flags = 0;
     if (out_len) *out_len = 0;
     if (!p || !d_off || !d_out_off || (n && !d_in) || (cap && !d_out)) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode == TRRE_MODE_FIND) return fail(TRRE_E_ARG, kFindOnlyMsg);
+    if (own_call_only(*p)) return fail(TRRE_E_ARG, own_call_only(*p));
     if (p->mode != TRRE_MODE_SCAN)
         return fail(TRRE_E_UNSUPPORTED, "error: strings are offered in scan mode only (a line of -m, -a, -ma prints zero or many newlines)");
     if (p->prints_newline)
@@ -2744,6 +2772,100 @@ int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     return find_on(p, st, stm, d_in, n, d_off, nrec, d_out, cap, d_match_off, match_cap, d_list_off, n_matches, out_len, static_cast<hipStream_t>(stream));
 }
 
+// ---- match spans (records_block.hpp) ---------------------------------------------------------------------------------------
+// The context holds the staged text (d_snap), the staging passes' ranks (d_find_off: nobody reads them here, k_str_stage writes
+// them), the framed text (d_framed) and, in d_rec behind the status word, cnt [3][tiles] and base [3][tiles + 1]
+static int span_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* d_start,
+                   int64_t* d_end, size_t span_cap, int64_t* d_list_off, size_t* n_matches, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    const int64_t T = str_tile_bytes();
+    const int64_t total = (int64_t)(n + nrec);                     // the staged text
+    const int64_t tiles = (total + T - 1) / T;
+    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
+    // 1. the offsets, on the device: nothing is written before they pass
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
+    const int bad = rec_status(cx, s, nullptr, nullptr);
+    if (bad < 0) return TRRE_E_DEVICE;
+    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 2. the staged text, as for the strings call; the ranks its stage pass leaves go into the library's own array
+    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
+    HIP_TRY(cx->d_find_off.reserve(nrec + 1, (nrec + 1) * 8));
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    StrArgs sa{};
+    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
+    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = cx->d_find_off;
+    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
+    launch_str_part(0, sa, part, tiles, s);
+    launch_str_stage(sa, tiles, s);
+    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    // 3. a string that holds a '\n' would be several lines: the staged newlines are the strings' closing ones exactly when they are nrec
+    uint64_t staged_nl = 0;
+    if (rec_status(cx, s, const_cast<uint64_t*>(sa.base) + tiles, &staged_nl) < 0) return TRRE_E_DEVICE;
+    if (staged_nl != nrec) return fail(TRRE_E_ARG, "error: a string holds a newline: it would be several lines, each with matches of its own");
+    // 4. the one scan: markers and position bytes
+    size_t m = 0;
+    const int rc = find_scan(p, st, cx->d_snap, (size_t)total, cx->d_framed, &m, s);
+    if (rc) return rc;                                      // (TRRE_E_DIVERGES: *n_matches stays 0)
+    if ((int64_t)m < total) return fail(TRRE_E_DEVICE, "error: the framed text is shorter than the staged text (internal)");
+    // 5. the markers per framed tile and before it; the table and the passes must agree before anything of the caller's is written
+    const int64_t ftiles = ((int64_t)m + T - 1) / T;
+    HIP_TRY(rec_room(cx, 2 * ftiles + 2));
+    SpanArgs pa{};
+    pa.src = cx->d_framed; pa.total = (int64_t)m; pa.nrec = (int64_t)nrec; pa.tiles = ftiles;
+    pa.cnt = cx->d_rec + 2; pa.base = cx->d_rec + 2 + 3 * ftiles;
+    launch_span_count(pa, s);
+    uint64_t tot[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {
+        uint64_t* base = const_cast<uint64_t*>(pa.base) + k * (ftiles + 1);
+        launch_chunk_scan(pa.cnt + k * ftiles, base, ftiles, s);
+        HIP_TRY(hipMemcpyAsync(&tot[k], base + ftiles, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (tot[0] != tot[1] || tot[2] != nrec || m != (size_t)total + 2 * tot[0])
+        return fail(TRRE_E_DEVICE, "error: the markers of the framed text do not add up (internal)");
+    const size_t found = (size_t)tot[0];
+    if (n_matches) *n_matches = found;
+    // 6. the spans and the list offsets — the list offsets alone when the spans do not fit
+    const bool over = found > span_cap;
+    pa.start = d_start; pa.end = d_end; pa.list_off = d_list_off; pa.n_match = over ? 0 : (int64_t)found; pa.lists_only = over ? 1u : 0u;
+    launch_span_emit(pa, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return over ? fail(TRRE_E_CAPACITY, "error: output buffer too small") : TRRE_OK;
+}
+
+int trre_span_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* d_start, int64_t* d_end,
+                             size_t span_cap, int64_t* d_list_off, size_t* n_matches, void* stream) {
+    g_scan_flags = 0;
+    if (n_matches) *n_matches = 0;
+    if (!p || !d_off || !d_list_off || (n && !d_in) || (span_cap && (!d_start || !d_end))) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: match spans take a program compiled with TRRE_MODE_SPANS");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || span_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    const size_t ob = (nrec + 1) * 8, sb = d_start ? span_cap * 8 : 0, eb = d_end ? span_cap * 8 : 0;
+    if (ranges_overlap(d_off, ob, d_list_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_list_off, ob, d_in, n) ||
+        ranges_overlap(d_start, sb, d_in, n) || ranges_overlap(d_start, sb, d_off, ob) || ranges_overlap(d_start, sb, d_list_off, ob) ||
+        ranges_overlap(d_end, eb, d_in, n) || ranges_overlap(d_end, eb, d_off, ob) || ranges_overlap(d_end, eb, d_list_off, ob) ||
+        ranges_overlap(d_start, sb, d_end, eb))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    DeviceState* st;
+    const int rc = current_state(p, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return span_on(p, st, d_in, n, d_off, nrec, d_start, d_end, span_cap, d_list_off, n_matches, static_cast<hipStream_t>(stream));
+}
+
 namespace {
 // grow one direction of a host slot (pinned staging + device buffer); need_pin false: the caller's own buffer is pinned, no staging on this side
 int slot_reserve(DeviceState::HostSlot& hs, bool input, size_t bytes, bool need_pin) {
@@ -3027,7 +3149,7 @@ static int host_overlap(const uint8_t* in, size_t n, const uint8_t* out, size_t 
 int trre_scan_host(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len, int device) {
     g_scan_flags = 0;
     if (!p || (n && !in) || (cap && !out)) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode == TRRE_MODE_FIND) return fail_empty(out_len, TRRE_E_ARG, kFindOnlyMsg);
+    if (own_call_only(*p)) return fail_empty(out_len, TRRE_E_ARG, own_call_only(*p));
     if (out_len) *out_len = 0;
     if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     if (n == 0) return TRRE_OK;
@@ -3131,7 +3253,7 @@ int scan_shards(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* o
 int trre_scan_host_multi(trre_prog* p, const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len, uint32_t device_mask) {
     g_scan_flags = 0;
     if (!p || (n && !in) || (cap && !out)) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode == TRRE_MODE_FIND) return fail_empty(out_len, TRRE_E_ARG, kFindOnlyMsg);
+    if (own_call_only(*p)) return fail_empty(out_len, TRRE_E_ARG, own_call_only(*p));
     if (out_len) *out_len = 0;
     if (host_overlap(in, n, out, cap)) return TRRE_E_ARG;
     int n_dev = 0;

@@ -1785,6 +1785,56 @@ __global__ __launch_bounds__(SG::THREADS) void k_find_unframe(StrArgs a) {
     str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
 }
 
+// ---- match spans (records_block.hpp; runtime.cpp: trre_span_device_strings) -------------------------------------------------
+// A, B and '\n' per framed tile
+__global__ __launch_bounds__(SG::THREADS) void k_span_count(SpanArgs a) {
+    __shared__ uint32_t wtot[3][SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    uint32_t c[3] = {0u, 0u, 0u};
+    span_mark_vecs<SG>(a, blockIdx.x, tid, nullptr, c);
+    for (int x = 0; x < 3; ++x) {
+        const uint64_t s = wave_sum(c[x]);
+        if ((tid & (kWave - 1)) == 0) wtot[x][tid / kWave] = (uint32_t)s;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        uint64_t t = 0;
+        for (int k = 0; k < SG::THREADS / kWave; ++k) t += wtot[tid][k];
+        a.cnt[(int64_t)tid * a.tiles + blockIdx.x] = t;
+    }
+}
+
+// The spans and the list offsets.  The mark images are staged into LDS by all threads and read across threads: a barrier stands
+// between span_mark_vecs and the first read (span_seg_count), the scans' own barriers between pre and span_fill_pv's readers,
+// and one more between pv and span_emit_pieces, which reads the words and prefixes of pieces other threads filled.
+__global__ __launch_bounds__(SG::THREADS) void k_span_emit(SpanArgs a) {
+    __shared__ uint16_t bits[3 * SG::NVEC];
+    __shared__ uint32_t pv_ab[SG::NVEC];
+    __shared__ uint32_t pv_nl[SG::NVEC];
+    __shared__ uint32_t pre_ab[SG::THREADS];
+    __shared__ uint32_t pre_nl[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    uint32_t c[3] = {0u, 0u, 0u};
+    span_mark_vecs<SG>(a, b, tid, bits, c);
+    __syncthreads();
+    uint32_t ab, nl;
+    span_seg_count<SG>(bits, tid, ab, nl);
+    rec_block_scan(ab, pre_ab, wtot);
+    rec_block_scan(nl, pre_nl, wtot);
+    span_fill_pv<SG>(bits, pre_ab[tid], pre_nl[tid], tid, pv_ab, pv_nl);
+    __syncthreads();
+    span_emit_pieces<SG>(a, b, tid, bits, pv_ab, pv_nl);
+}
+
+void launch_span_count(const SpanArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_span_count, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_span_emit(const SpanArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_span_emit, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+
 void launch_match_verdict(int sym_bits, const MatchArgs& a, void* stream) {
     const int64_t groups = (a.nrec + kMatchThreads - 1) / kMatchThreads;
     const dim3 grid((unsigned)(groups < 1 ? 1 : groups > 256 * 16 ? 256 * 16 : groups)), block(kMatchThreads);
