@@ -121,6 +121,39 @@ def _bytes(x):
     return x.encode("latin-1") if isinstance(x, str) else bytes(x)
 
 
+def _column(values, offsets, stream):
+    """a column of strings as the device calls take it, checked: (n, nrec, the stream's handle)"""
+    import torch
+    assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
+    assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
+    s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
+    return values.numel(), offsets.numel() - 1, s
+
+
+def _retry_capacity(call, out, m, device):
+    """call(out) and, on E_CAPACITY, once more with a buffer of the size the call reported in m: (rc, out)"""
+    import torch
+    with torch.cuda.device(device):
+        rc = call(out)
+        if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
+            out = torch.empty(m.value + 16, dtype=torch.uint8, device=device)
+            rc = call(out)
+    return rc, out
+
+
+def _pack(records, device):
+    """a list of bytes as a column on the device: (recs, host offsets, values, offsets)"""
+    import numpy as np
+    import torch
+    recs = [_bytes(r) for r in records]
+    off = np.zeros(len(recs) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in recs], out=off[1:])
+    dev = torch.device("cuda", device)
+    packed = b"".join(recs)
+    values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
+    return recs, off, values, torch.from_numpy(off).to(dev)
+
+
 class Program:
     """A compiled pattern bound to one engine."""
 
@@ -271,24 +304,17 @@ class Program:
         record is scanned as if it were a file of its own.  Returns (out_values, out_offsets): record i's output is
         out_values[out_offsets[i]:out_offsets[i+1]].  out may be values itself (in place); a too small out is replaced."""
         import torch
-        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
-        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
-        n, nrec = values.numel(), offsets.numel() - 1
+        n, nrec, s = _column(values, offsets, stream)
         if out is None:
             out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
         if out_offsets is None:
             out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
-        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
         m = ctypes.c_size_t()
 
         def call(o):
             return lib().trre_scan_device_records(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o.data_ptr(), o.numel(),
                                                   out_offsets.data_ptr(), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(out)
-            if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
-                out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
-                rc = call(out)
+        rc, out = _retry_capacity(call, out, m, values.device)
         if rc == E_DIVERGES:
             raise TrreError(rc, lib().trre_last_error().decode("latin-1"), out[:m.value])
         _check(rc)
@@ -302,24 +328,17 @@ class Program:
         (out_values, out_offsets): string i's output is out_values[out_offsets[i]:out_offsets[i+1]].  out may be values itself
         (in place); a too small out is replaced.  A string the reference does not survive raises TrreError with partial=None."""
         import torch
-        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
-        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
-        n, nrec = values.numel(), offsets.numel() - 1
+        n, nrec, s = _column(values, offsets, stream)
         if out is None:
             out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
         if out_offsets is None:
             out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
-        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
         m = ctypes.c_size_t()
 
         def call(o):
             return lib().trre_scan_device_strings(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o.data_ptr(), o.numel(),
                                                   out_offsets.data_ptr(), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(out)
-            if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
-                out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
-                rc = call(out)
+        rc, out = _retry_capacity(call, out, m, values.device)
         _check(rc)
         return out[:m.value], out_offsets
 
@@ -338,25 +357,18 @@ class Program:
         valid is a torch.bool tensor of nrec entries; with packed=True it is the Arrow validity bitmap as the library wrote it
         (uint8, 8 * ceil(nrec / 64) bytes, bit i & 7 of byte i >> 3).  out may be values itself; a too small out is replaced."""
         import torch
-        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
-        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
-        n, nrec = values.numel(), offsets.numel() - 1
+        n, nrec, s = _column(values, offsets, stream)
         if out is None:
             out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
         if out_offsets is None:
             out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
         words = torch.zeros(max((nrec + 63) // 64, 1), dtype=torch.int64, device=values.device)     # (8-byte aligned)
-        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
         m, k = ctypes.c_size_t(), ctypes.c_size_t()
 
         def call(o):
             return lib().trre_match_device_strings(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o.data_ptr(), o.numel(),
                                                    out_offsets.data_ptr(), words.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(out)
-            if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
-                out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
-                rc = call(out)
+        rc, out = _retry_capacity(call, out, m, values.device)
         _check(rc)
         bitmap = words.view(torch.uint8)[:8 * ((nrec + 63) // 64)]
         if packed:
@@ -367,15 +379,8 @@ class Program:
 
     def match_list(self, records, device=0):
         """list of bytes in -> list out: what an accepted string becomes (bytes), None for a rejected one (through match_strings)"""
-        import numpy as np
-        import torch
-        recs = [_bytes(r) for r in records]
-        off = np.zeros(len(recs) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in recs], out=off[1:])
-        dev = torch.device("cuda", device)
-        packed = b"".join(recs)
-        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
-        out, out_off, valid = self.match_strings(values, torch.from_numpy(off).to(dev))
+        recs, off, values, offsets = _pack(records, device)
+        out, out_off, valid = self.match_strings(values, offsets)
         blob = out.cpu().numpy().tobytes()
         o = out_off.cpu().numpy().tolist()
         ok = valid.cpu().numpy().tolist()
@@ -387,11 +392,8 @@ class Program:
         list_offsets[i] .. list_offsets[i + 1] - 1, and match j's output is out[match_offsets[j]:match_offsets[j + 1]].  Two
         calls: the size query, then the one that fills buffers of exactly that size."""
         import torch
-        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
-        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
-        n, nrec = values.numel(), offsets.numel() - 1
+        n, nrec, s = _column(values, offsets, stream)
         list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
-        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
         m, k = ctypes.c_size_t(), ctypes.c_size_t()
 
         def call(o, cap, mo, mcap):
@@ -409,15 +411,8 @@ class Program:
 
     def find_list(self, records, device=0):
         """list of bytes in -> list of lists of bytes out: every match's output, string by string (through find_strings)"""
-        import numpy as np
-        import torch
-        recs = [_bytes(r) for r in records]
-        off = np.zeros(len(recs) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in recs], out=off[1:])
-        dev = torch.device("cuda", device)
-        packed = b"".join(recs)
-        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
-        out, match_off, list_off = self.find_strings(values, torch.from_numpy(off).to(dev))
+        recs, off, values, offsets = _pack(records, device)
+        out, match_off, list_off = self.find_strings(values, offsets)
         blob = out.cpu().numpy().tobytes()
         mo = match_off.cpu().numpy().tolist()
         lo = list_off.cpu().numpy().tolist()
@@ -426,11 +421,8 @@ class Program:
     def _span_call(self, values, offsets, starts, ends, cap, stream):
         """one trre_span_device_strings call: (rc, n_matches, list_offsets)"""
         import torch
-        assert values.is_cuda and values.dtype == torch.uint8 and values.dim() == 1 and values.is_contiguous()
-        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
-        n, nrec = values.numel(), offsets.numel() - 1
+        n, nrec, s = _column(values, offsets, stream)
         list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
-        s = stream if stream is not None else torch.cuda.current_stream(values.device).cuda_stream
         k = ctypes.c_size_t()
         with torch.cuda.device(values.device):
             rc = lib().trre_span_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec,
@@ -465,29 +457,15 @@ class Program:
     def span_list(self, records, device=0):
         """list of bytes in -> per string a list of (start, end) relative to that string, as m.span() of re.finditer (through
         span_strings)"""
-        import numpy as np
-        import torch
-        recs = [_bytes(r) for r in records]
-        off = np.zeros(len(recs) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in recs], out=off[1:])
-        dev = torch.device("cuda", device)
-        packed = b"".join(recs)
-        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
-        starts, ends, list_off = self.span_strings(values, torch.from_numpy(off).to(dev))
+        recs, off, values, offsets = _pack(records, device)
+        starts, ends, list_off = self.span_strings(values, offsets)
         st, en, lo = starts.cpu().numpy().tolist(), ends.cpu().numpy().tolist(), list_off.cpu().numpy().tolist()
         return [[(st[j] - int(off[i]), en[j] - int(off[i])) for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
 
     @staticmethod
     def _map_list(records, device, scan):
-        import numpy as np
-        import torch
-        recs = [_bytes(r) for r in records]
-        off = np.zeros(len(recs) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in recs], out=off[1:])
-        dev = torch.device("cuda", device)
-        packed = b"".join(recs)
-        values = torch.frombuffer(bytearray(packed or b"\0"), dtype=torch.uint8)[:len(packed)].to(dev)
-        out, out_off = scan(values, torch.from_numpy(off).to(dev))
+        recs, off, values, offsets = _pack(records, device)
+        out, out_off = scan(values, offsets)
         blob = out.cpu().numpy().tobytes()
         o = out_off.cpu().numpy().tolist()
         return [blob[o[i]:o[i + 1]] for i in range(len(recs))]

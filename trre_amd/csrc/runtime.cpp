@@ -166,7 +166,7 @@ struct ScanCtx {
     DevBuf<uint8_t> d_sym;            // guided families: one symbol per input byte (bytes)
     DevBuf<uint8_t> d_snap;           // an in-place scan (d_in == d_out): a copy of its input, which every launch and fallback reads;
                                       // trre_scan_device_records / _strings: the staged copy, which the scan reads (bytes)
-    DevBuf<uint64_t> d_rec;           // trre_scan_device_records: status word, then part [tiles + 1], cnt [tiles], base [tiles + 1] (tiles)
+    DevBuf<uint64_t> d_rec;           // the five column calls: status word, then what the pass that runs carves (rec_carve; spans: span_on) (tiles)
     DevBuf<uint8_t> d_gen_out;        // generator modes: the enumeration's output before it goes down (bytes)
     DevBuf<uint8_t> d_framed;         // trre_scan_device_strings: the scan's output with every record's closing '\n' still in it (bytes)
     DevBuf<uint64_t> d_match;         // trre_match_device_strings: accepted strings per group of 256, then their exclusive scan [groups + 1] (groups)
@@ -2268,13 +2268,21 @@ int trre_scan_device(trre_prog* p, const uint8_t* d_in, size_t n, uint8_t* d_out
     return finish(p, st, &st->ctx, out_len);
 }
 
-// ---- ragged records (records_block.hpp) ----------------------------------------------------------------------------------
-// status word, part [tiles + 1], cnt [tiles], base [tiles + 1]
+// ---- the host passes the column calls share (records_block.hpp) ----------------------------------------------
+// ScanCtx::d_rec: the status word, then part [tiles + 1], cnt [tiles], base [tiles + 1] for the tiles of the pass that runs
+struct RecCarve {
+    int64_t* part;
+    uint64_t* cnt;
+    uint64_t* base;
+};
 static hipError_t rec_room(ScanCtx* cx, int64_t tiles) { return cx->d_rec.reserve((size_t)tiles, (size_t)(3 * tiles + 3) * 8); }
-static void rec_carve(ScanCtx* cx, int64_t tiles, trre::RecArgs& a) {
-    a.part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
-    a.cnt = cx->d_rec + 2 + tiles;
-    a.base = cx->d_rec + 2 + 2 * tiles;
+// room for `tiles`, then the three arrays: carved after growing, which moves them
+static int rec_carve(ScanCtx* cx, int64_t tiles, RecCarve* c) {
+    HIP_TRY(rec_room(cx, tiles));
+    c->part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
+    c->cnt = cx->d_rec + 2 + tiles;
+    c->base = cx->d_rec + 2 + 2 * tiles;
+    return TRRE_OK;
 }
 static int rec_status(ScanCtx* cx, hipStream_t s, uint64_t* extra_dev, uint64_t* extra) {
     uint32_t bad = 0;
@@ -2284,6 +2292,102 @@ static int rec_status(ScanCtx* cx, hipStream_t s, uint64_t* extra_dev, uint64_t*
     return bad ? 1 : 0;
 }
 
+// The caller's offsets, on the device, before anything of the caller's is written: k_rec_check and its status word.  d_rec
+// first gets room for `tiles`, the tiles the caller stages next (the status word at the least).
+static int rec_check_offsets(ScanCtx* cx, int64_t tiles, const int64_t* d_off, size_t nrec, size_t n, hipStream_t s) {
+    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    trre::launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
+    const int bad = rec_status(cx, s, nullptr, nullptr);
+    if (bad < 0) return TRRE_E_DEVICE;
+    return bad ? fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease") : TRRE_OK;
+}
+
+// The staged text of a column of strings, n + nrec bytes in d_snap (16-byte aligned, whole vectors): k_str_part(0), k_str_stage,
+// k_chunk_scan.  The stage pass leaves the strings' tile-local ranks in `ranks` [nrec + 1]; *sa is what the passes ran with, for
+// k_str_rank where the caller wants the ranks whole.
+static int str_stage_text(ScanCtx* cx, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* ranks, hipStream_t s,
+                          trre::StrArgs* sa) {
+    using namespace trre;
+    const int64_t T = str_tile_bytes();
+    const int64_t total = (int64_t)(n + nrec), tiles = (total + T - 1) / T;
+    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
+    RecCarve c;
+    const int rc = rec_carve(cx, tiles, &c);
+    if (rc) return rc;
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    *sa = StrArgs{};
+    sa->src_v0 = d_in - a0; sa->vbeg = a0; sa->total = total; sa->dst = cx->d_snap;
+    sa->off = d_off; sa->nrec = (int64_t)nrec; sa->out_off = ranks;
+    sa->part = c.part; sa->cnt = c.cnt; sa->base = c.base;
+    launch_str_part(0, *sa, c.part, tiles, s);
+    launch_str_stage(*sa, tiles, s);
+    launch_chunk_scan(c.cnt, c.base, tiles, s);
+    return TRRE_OK;
+}
+// ... and its newline total, base[tiles] of those passes, read back: nrec exactly when no string holds a '\n'
+static int str_staged_newlines(ScanCtx* cx, const trre::StrArgs& sa, hipStream_t s, uint64_t* total) {
+    const int64_t T = trre::str_tile_bytes();
+    return rec_status(cx, s, const_cast<uint64_t*>(sa.base) + (sa.total + T - 1) / T, total);
+}
+
+// Record i's output ends just past newline number R_i of the text [vbeg, vend) over in_v0, R_i parked in out_off[i + 1]:
+// k_rec_count, k_chunk_scan, k_rec_part(1), k_rec_locate put the end in its place.  One read-back: 1 when a rank fell outside
+// its tile, *last = out_off[nrec] and, where the caller asks for it, *newlines = the text's newline total.
+static int rec_locate_ends(ScanCtx* cx, const uint8_t* in_v0, int64_t vbeg, int64_t vend, size_t nrec, int64_t* out_off, hipStream_t s,
+                           uint64_t* last, uint64_t* newlines) {
+    using namespace trre;
+    const int64_t T = rec_tile_bytes(), tiles = (vend + T - 1) / T;
+    RecCarve c;
+    const int rc = rec_carve(cx, tiles, &c);
+    if (rc) return rc;
+    RecArgs a{};
+    a.in_v0 = in_v0; a.vbeg = vbeg; a.vend = vend; a.nrec = (int64_t)nrec; a.out_off = out_off;
+    a.part = c.part; a.cnt = c.cnt; a.base = c.base;
+    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
+    launch_rec_count(a, tiles, s);
+    launch_chunk_scan(c.cnt, c.base, tiles, s);
+    launch_rec_part(1, a, tiles, s);
+    launch_rec_locate(a, tiles, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
+    if (newlines) HIP_TRY(hipMemcpyAsync(newlines, c.base + tiles, 8, hipMemcpyDeviceToHost, s));
+    return rec_status(cx, s, reinterpret_cast<uint64_t*>(out_off + nrec), last);
+}
+
+// '\n' per string tile (16 KiB) of a framed text of m bytes and before every tile: k_match_count, k_chunk_scan into a fresh
+// carve; *base [tiles + 1]
+static int str_tile_newlines(ScanCtx* cx, const uint8_t* framed, int64_t m, hipStream_t s, const uint64_t** base) {
+    using namespace trre;
+    const int64_t T = str_tile_bytes(), tiles = (m + T - 1) / T;
+    RecCarve c;
+    const int rc = rec_carve(cx, tiles, &c);
+    if (rc) return rc;
+    RecArgs a{};
+    a.in_v0 = framed; a.vbeg = 0; a.vend = m;
+    a.part = c.part; a.cnt = c.cnt; a.base = c.base;
+    launch_match_count(a, tiles, s);
+    launch_chunk_scan(c.cnt, c.base, tiles, s);
+    *base = c.base;
+    return TRRE_OK;
+}
+
+// A framed text of m bytes without its nrec closing newlines into dst, by the located offsets in out_off, which become the
+// final ones: k_str_part(1), k_str_unframe
+static int str_unframe_located(ScanCtx* cx, const uint8_t* framed, int64_t m, uint8_t* dst, size_t nrec, int64_t* out_off, hipStream_t s) {
+    using namespace trre;
+    const int64_t T = str_tile_bytes(), tiles = (m + T - 1) / T;
+    RecCarve c;
+    const int rc = rec_carve(cx, tiles, &c);
+    if (rc) return rc;
+    StrArgs a{};
+    a.src_v0 = framed; a.total = m; a.dst = dst; a.dst_len = m - (int64_t)nrec;
+    a.nrec = (int64_t)nrec; a.out_off = out_off; a.part = c.part;
+    launch_str_part(1, a, c.part, tiles, s);
+    launch_str_unframe(a, tiles, s);
+    HIP_TRY(hipGetLastError());
+    return TRRE_OK;
+}
+
+// ---- ragged records (records_block.hpp) ----------------------------------------------------------------------------------
 static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
                       size_t cap, int64_t* d_out_off, size_t* out_len, hipStream_t s) {
     using namespace trre;
@@ -2291,14 +2395,9 @@ static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     const int64_t T = rec_tile_bytes();
     const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
     const int64_t tiles = n ? (a0 + (int64_t)n + T - 1) / T : 0;
-    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
-    int rc;
     // 1. the offsets, on the device: nothing is written before they pass
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
-    const int bad = rec_status(cx, s, nullptr, nullptr);
-    if (bad < 0) return TRRE_E_DEVICE;
-    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    int rc = rec_check_offsets(cx, tiles, d_off, nrec, n, s);
+    if (rc) return rc;
     if (n == 0) {                                        // every record is empty
         HIP_TRY(hipMemsetAsync(d_out_off, 0, (nrec + 1) * 8, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -2309,7 +2408,10 @@ static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     RecArgs ra{};
     ra.in_v0 = d_in - a0; ra.snap_v0 = cx->d_snap; ra.vbeg = a0; ra.vend = a0 + (int64_t)n;
     ra.off = d_off; ra.nrec = (int64_t)nrec; ra.out_off = d_out_off; ra.keep = d_in == d_out ? 1u : 0u;
-    rec_carve(cx, tiles, ra);
+    RecCarve c;
+    rc = rec_carve(cx, tiles, &c);
+    if (rc) return rc;
+    ra.part = c.part; ra.cnt = c.cnt; ra.base = c.base;
     launch_rec_part(0, ra, tiles, s);
     launch_rec_stage(ra, tiles, s);
     launch_chunk_scan(ra.cnt, const_cast<uint64_t*>(ra.base), tiles, s);
@@ -2333,19 +2435,8 @@ static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     }
     // 4. record i's output ends just past output newline number R_i
     const int64_t b0 = (int64_t)(reinterpret_cast<uintptr_t>(d_out) & 15u);
-    const int64_t otiles = (b0 + (int64_t)m + T - 1) / T;
-    HIP_TRY(rec_room(cx, otiles));
-    RecArgs oa = ra;
-    oa.in_v0 = d_out - b0; oa.vbeg = b0; oa.vend = b0 + (int64_t)m;
-    rec_carve(cx, otiles, oa);
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_count(oa, otiles, s);
-    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
-    launch_rec_part(1, oa, otiles, s);
-    launch_rec_locate(oa, otiles, d_bad, s);
     uint64_t last = 0;
-    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(d_out_off + nrec), &last);
+    const int lost = rec_locate_ends(cx, d_out - b0, b0, b0 + (int64_t)m, nrec, d_out_off, s, &last, nullptr);
     if (lost < 0) return TRRE_E_DEVICE;
     if (lost || last != m) return fail(TRRE_E_DEVICE, "error: the records' output offsets do not add up (internal)");
     return TRRE_OK;
@@ -2376,38 +2467,25 @@ int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const 
 }
 
 // ---- packed strings (records_block.hpp) ------------------------------------------------------------------------------------
-// d_rec, string tiles (16 KiB): status word, part [tiles + 1], cnt [tiles], base [tiles + 1]
+// d_rec holds the passes' arrays over string tiles (16 KiB) while staging and unframing, over record tiles (64 KiB) in between
 static int strings_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
                       size_t cap, int64_t* d_out_off, size_t* out_len, hipStream_t s) {
     using namespace trre;
     ScanCtx* cx = &st->ctx;
     const int64_t T = str_tile_bytes();
     const int64_t total = (int64_t)(n + nrec);                     // the staged text
-    const int64_t tiles = (total + T - 1) / T;
-    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
-    int rc;
     // 1. the offsets, on the device: nothing is written before they pass
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
-    const int bad = rec_status(cx, s, nullptr, nullptr);
-    if (bad < 0) return TRRE_E_DEVICE;
-    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    int rc = rec_check_offsets(cx, (total + T - 1) / T, d_off, nrec, n, s);
+    if (rc) return rc;
     if (nrec == 0) {
         HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
         HIP_TRY(hipStreamSynchronize(s));
         return TRRE_OK;
     }
     // 2. the staged text (the snapshot buffer, 16-byte aligned, whole vectors) and the ranks
-    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
-    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    StrArgs sa{};
-    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
-    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = d_out_off;
-    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
-    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
-    launch_str_part(0, sa, part, tiles, s);
-    launch_str_stage(sa, tiles, s);
-    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    StrArgs sa;
+    rc = str_stage_text(cx, d_in, n, d_off, nrec, d_out_off, s, &sa);
+    if (rc) return rc;
     launch_str_rank(sa, s);
     // 3. the plain scan of the staged text into the framed buffer, family as chosen for the program
     const size_t fcap = cap + nrec;
@@ -2420,33 +2498,13 @@ static int strings_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     if (rc) return rc;                                     // (TRRE_E_DIVERGES: *out_len stays 0)
     if (m < nrec) return fail(TRRE_E_DEVICE, "error: the strings' output offsets do not add up (internal)");
     // 4. record i's framed output ends just past framed newline number R_i
-    const int64_t RT = rec_tile_bytes();
-    const int64_t otiles = ((int64_t)m + RT - 1) / RT;
-    HIP_TRY(rec_room(cx, otiles));
-    RecArgs oa{};
-    oa.in_v0 = cx->d_framed; oa.vbeg = 0; oa.vend = (int64_t)m; oa.nrec = (int64_t)nrec; oa.out_off = d_out_off;
-    rec_carve(cx, otiles, oa);
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_count(oa, otiles, s);
-    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
-    launch_rec_part(1, oa, otiles, s);
-    launch_rec_locate(oa, otiles, d_bad, s);
     uint64_t last = 0;
-    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(d_out_off + nrec), &last);
+    const int lost = rec_locate_ends(cx, cx->d_framed, 0, (int64_t)m, nrec, d_out_off, s, &last, nullptr);
     if (lost < 0) return TRRE_E_DEVICE;
     if (lost || last != m) return fail(TRRE_E_DEVICE, "error: the strings' output offsets do not add up (internal)");
     // 5. the framed output without the closing newlines into the caller's buffer, and the final offsets
-    const int64_t utiles = ((int64_t)m + T - 1) / T;
-    HIP_TRY(rec_room(cx, utiles));
-    StrArgs ua{};
-    ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - nrec);
-    ua.nrec = (int64_t)nrec; ua.out_off = d_out_off;
-    part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
-    ua.part = part;
-    launch_str_part(1, ua, part, utiles, s);
-    launch_str_unframe(ua, utiles, s);
-    HIP_TRY(hipGetLastError());
+    rc = str_unframe_located(cx, cx->d_framed, (int64_t)m, d_out, nrec, d_out_off, s);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if (out_len) *out_len = m - nrec;
     return TRRE_OK;
@@ -2484,33 +2542,20 @@ static int match_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n
     ScanCtx* cx = &st->ctx;
     const int64_t T = str_tile_bytes();
     const int64_t total = (int64_t)(n + nrec);                     // the staged text
-    const int64_t tiles = (total + T - 1) / T;
-    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
-    int rc;
     // 1. the offsets, on the device: nothing is written before they pass
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
-    const int bad = rec_status(cx, s, nullptr, nullptr);
-    if (bad < 0) return TRRE_E_DEVICE;
-    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    int rc = rec_check_offsets(cx, (total + T - 1) / T, d_off, nrec, n, s);
+    if (rc) return rc;
     if (nrec == 0) {
         HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
         HIP_TRY(hipStreamSynchronize(s));
         return TRRE_OK;
     }
     // 2. the staged text, as for the strings call; its '\n' are the strings' closing ones and nothing else exactly when their number is nrec
-    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
-    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    StrArgs sa{};
-    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
-    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = d_out_off;
-    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
-    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
-    launch_str_part(0, sa, part, tiles, s);
-    launch_str_stage(sa, tiles, s);
-    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    StrArgs sa;
+    rc = str_stage_text(cx, d_in, n, d_off, nrec, d_out_off, s, &sa);
+    if (rc) return rc;
     uint64_t staged_nl = 0;
-    if (rec_status(cx, s, const_cast<uint64_t*>(sa.base) + tiles, &staged_nl) < 0) return TRRE_E_DEVICE;
+    if (str_staged_newlines(cx, sa, s, &staged_nl) < 0) return TRRE_E_DEVICE;
     if (staged_nl != nrec) return fail(TRRE_E_ARG, "error: a string holds a newline: it would be several lines with several verdicts");
     // 3. the plain match scan of the staged text into the framed buffer, on the general guided family: its count pass always runs, and with
     // it the backward pass, whose symbols the verdicts are read from (the length-preserving family does not launch into too small a buffer)
@@ -2549,34 +2594,21 @@ static int match_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n
         return TRRE_OK;
     }
     // 5. string i's framed output ends just past framed newline number M_i
-    const int64_t RT = rec_tile_bytes();
-    const int64_t otiles = ((int64_t)m + RT - 1) / RT, utiles = ((int64_t)m + T - 1) / T;
+    const int64_t utiles = ((int64_t)m + T - 1) / T;
     HIP_TRY(rec_room(cx, utiles));                          // (the compaction's tiles are the smaller ones: room for both)
-    RecArgs oa{};
-    oa.in_v0 = cx->d_framed; oa.vbeg = 0; oa.vend = (int64_t)m; oa.nrec = (int64_t)nrec; oa.out_off = d_out_off;
-    rec_carve(cx, otiles, oa);
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_count(oa, otiles, s);
-    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
-    launch_rec_part(1, oa, otiles, s);
-    launch_rec_locate(oa, otiles, d_bad, s);
-    uint64_t last[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(&last[1], oa.base + otiles, 8, hipMemcpyDeviceToHost, s));
-    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(d_out_off + nrec), &last[0]);
+    uint64_t last = 0, framed_nl = 0;
+    const int lost = rec_locate_ends(cx, cx->d_framed, 0, (int64_t)m, nrec, d_out_off, s, &last, &framed_nl);
     if (lost < 0) return TRRE_E_DEVICE;
-    if (lost || last[0] != m || last[1] != matched) return fail(TRRE_E_DEVICE, "error: the matched strings' output offsets do not add up (internal)");
+    if (lost || last != m || framed_nl != matched) return fail(TRRE_E_DEVICE, "error: the matched strings' output offsets do not add up (internal)");
     // 6. the final offsets; the framed output without its newlines into the caller's buffer
     launch_match_final(ma, s);
-    RecArgs ca{};
-    ca.in_v0 = cx->d_framed; ca.vbeg = 0; ca.vend = (int64_t)m;
-    rec_carve(cx, utiles, ca);
-    launch_match_count(ca, utiles, s);
-    launch_chunk_scan(ca.cnt, const_cast<uint64_t*>(ca.base), utiles, s);
+    const uint64_t* before = nullptr;                       // '\n' before every tile of the compaction
+    rc = str_tile_newlines(cx, cx->d_framed, (int64_t)m, s, &before);
+    if (rc) return rc;
     StrArgs ua{};
     ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - matched);
     ua.nrec = (int64_t)nrec; ua.out_off = d_out_off;
-    ua.part = reinterpret_cast<const int64_t*>(ca.base);
+    ua.part = reinterpret_cast<const int64_t*>(before);
     launch_match_unframe(ua, utiles, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -2640,14 +2672,9 @@ static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_
     ScanCtx* cx = &st->ctx;
     const int64_t T = str_tile_bytes();
     const int64_t total = (int64_t)(n + nrec);                     // the staged text
-    const int64_t tiles = (total + T - 1) / T;
-    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
     // 1. the offsets, on the device: nothing is written before they pass
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
-    const int bad = rec_status(cx, s, nullptr, nullptr);
-    if (bad < 0) return TRRE_E_DEVICE;
-    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    int rc = rec_check_offsets(cx, (total + T - 1) / T, d_off, nrec, n, s);
+    if (rc) return rc;
     if (nrec == 0) {
         HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
         if (d_match_off) HIP_TRY(hipMemsetAsync(d_match_off, 0, 8, s));
@@ -2656,57 +2683,32 @@ static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_
     }
     // 2. the staged text and the strings' ranks, as for the strings call — the ranks into the library's own array: the caller's
     // are not written before the strings have passed (3)
-    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
     HIP_TRY(cx->d_find_off.reserve(nrec + 1, (nrec + 1) * 8));
     int64_t* loff = cx->d_find_off;
-    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    StrArgs sa{};
-    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
-    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = loff;
-    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
-    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
-    launch_str_part(0, sa, part, tiles, s);
-    launch_str_stage(sa, tiles, s);
-    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    StrArgs sa;
+    rc = str_stage_text(cx, d_in, n, d_off, nrec, loff, s, &sa);
+    if (rc) return rc;
     launch_str_rank(sa, s);
     // 3. a string that holds a '\n' would be several lines: the staged newlines are the strings' closing ones exactly when they are nrec
     uint64_t staged_nl = 0;
-    if (rec_status(cx, s, const_cast<uint64_t*>(sa.base) + tiles, &staged_nl) < 0) return TRRE_E_DEVICE;
+    if (str_staged_newlines(cx, sa, s, &staged_nl) < 0) return TRRE_E_DEVICE;
     if (staged_nl != nrec) return fail(TRRE_E_ARG, "error: a string holds a newline: it would be several lines, each with matches of its own");
     // 4. the marks scan, and its unframing by the strings call's passes: string i's marks end just past framed newline number i + 1,
     // and the unframed offsets are the list offsets
     size_t mm = 0;
-    int rc = find_scan(p->find_marks.get(), stm, cx->d_snap, (size_t)total, stm->ctx.d_framed, &mm, s);
+    rc = find_scan(p->find_marks.get(), stm, cx->d_snap, (size_t)total, stm->ctx.d_framed, &mm, s);
     if (rc) return rc;                                      // (TRRE_E_DIVERGES: *out_len stays 0)
     if (mm < nrec) return fail(TRRE_E_DEVICE, "error: the list offsets do not add up (internal)");
     const uint8_t* marks = stm->ctx.d_framed;
     const size_t found = mm - nrec;
-    const int64_t RT = rec_tile_bytes();
-    const int64_t otiles = ((int64_t)mm + RT - 1) / RT, mtiles = ((int64_t)mm + T - 1) / T;
-    HIP_TRY(rec_room(cx, std::max(otiles, mtiles)));
+    HIP_TRY(rec_room(cx, ((int64_t)mm + T - 1) / T));       // (the unframing's tiles are the smaller ones: room for both)
     HIP_TRY(cx->d_find_marks.reserve(found + 64, found + 64));
-    RecArgs oa{};
-    oa.in_v0 = marks; oa.vbeg = 0; oa.vend = (int64_t)mm; oa.nrec = (int64_t)nrec; oa.out_off = loff;
-    rec_carve(cx, otiles, oa);
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(cx->d_rec.p);
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_count(oa, otiles, s);
-    launch_chunk_scan(oa.cnt, const_cast<uint64_t*>(oa.base), otiles, s);
-    launch_rec_part(1, oa, otiles, s);
-    launch_rec_locate(oa, otiles, d_bad, s);
-    uint64_t last[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(&last[1], oa.base + otiles, 8, hipMemcpyDeviceToHost, s));
-    const int lost = rec_status(cx, s, reinterpret_cast<uint64_t*>(loff + nrec), &last[0]);
+    uint64_t last = 0, marks_nl = 0;
+    const int lost = rec_locate_ends(cx, marks, 0, (int64_t)mm, nrec, loff, s, &last, &marks_nl);
     if (lost < 0) return TRRE_E_DEVICE;
-    if (lost || last[0] != mm || last[1] != nrec) return fail(TRRE_E_DEVICE, "error: the list offsets do not add up (internal)");
-    StrArgs ma{};
-    ma.src_v0 = marks; ma.total = (int64_t)mm; ma.dst = cx->d_find_marks; ma.dst_len = (int64_t)found;
-    ma.nrec = (int64_t)nrec; ma.out_off = loff;
-    part = reinterpret_cast<int64_t*>(cx->d_rec + 1);       // (d_rec may have grown)
-    ma.part = part;
-    launch_str_part(1, ma, part, mtiles, s);
-    launch_str_unframe(ma, mtiles, s);
-    HIP_TRY(hipGetLastError());
+    if (lost || last != mm || marks_nl != nrec) return fail(TRRE_E_DEVICE, "error: the list offsets do not add up (internal)");
+    rc = str_unframe_located(cx, marks, (int64_t)mm, cx->d_find_marks, nrec, loff, s);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_list_off, loff, (nrec + 1) * 8, hipMemcpyDeviceToDevice, s));
     // 5. the texts scan: every match's output and a '\n' — as many as there are marks
     size_t m = 0;
@@ -2714,15 +2716,12 @@ static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_
     if (rc) return rc;
     const int64_t utiles = ((int64_t)m + T - 1) / T;
     uint64_t closed = 0;
-    RecArgs ca{};
+    const uint64_t* before = nullptr;                       // '\n' before every tile of the texts
     if (m) {
-        HIP_TRY(rec_room(cx, utiles));
-        ca.in_v0 = cx->d_framed; ca.vbeg = 0; ca.vend = (int64_t)m;
-        rec_carve(cx, utiles, ca);
-        launch_match_count(ca, utiles, s);
-        launch_chunk_scan(ca.cnt, const_cast<uint64_t*>(ca.base), utiles, s);
+        rc = str_tile_newlines(cx, cx->d_framed, (int64_t)m, s, &before);
+        if (rc) return rc;
         HIP_TRY(hipGetLastError());
-        if (rec_status(cx, s, const_cast<uint64_t*>(ca.base) + utiles, &closed) < 0) return TRRE_E_DEVICE;
+        if (rec_status(cx, s, const_cast<uint64_t*>(before) + utiles, &closed) < 0) return TRRE_E_DEVICE;
     } else {
         HIP_TRY(hipStreamSynchronize(s));
     }
@@ -2737,7 +2736,7 @@ static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_
         StrArgs ua{};
         ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - found);
         ua.nrec = (int64_t)found; ua.out_off = d_match_off;
-        ua.part = reinterpret_cast<const int64_t*>(ca.base);
+        ua.part = reinterpret_cast<const int64_t*>(before);
         launch_find_unframe(ua, utiles, s);
         HIP_TRY(hipGetLastError());
     }
@@ -2781,46 +2780,36 @@ static int span_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n,
     ScanCtx* cx = &st->ctx;
     const int64_t T = str_tile_bytes();
     const int64_t total = (int64_t)(n + nrec);                     // the staged text
-    const int64_t tiles = (total + T - 1) / T;
-    HIP_TRY(rec_room(cx, std::max<int64_t>(tiles, 1)));
     // 1. the offsets, on the device: nothing is written before they pass
-    HIP_TRY(hipMemsetAsync(cx->d_rec, 0, 8, s));
-    launch_rec_check(d_off, (int64_t)nrec, (int64_t)n, reinterpret_cast<uint32_t*>(cx->d_rec.p), s);
-    const int bad = rec_status(cx, s, nullptr, nullptr);
-    if (bad < 0) return TRRE_E_DEVICE;
-    if (bad) return fail(TRRE_E_ARG, "error: record offsets must start at 0, end at n and never decrease");
+    int rc = rec_check_offsets(cx, (total + T - 1) / T, d_off, nrec, n, s);
+    if (rc) return rc;
     if (nrec == 0) {
         HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
         HIP_TRY(hipStreamSynchronize(s));
         return TRRE_OK;
     }
     // 2. the staged text, as for the strings call; the ranks its stage pass leaves go into the library's own array
-    HIP_TRY(cx->d_snap.reserve((size_t)total + 64, (size_t)total + 64));
     HIP_TRY(cx->d_find_off.reserve(nrec + 1, (nrec + 1) * 8));
-    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    StrArgs sa{};
-    sa.src_v0 = d_in - a0; sa.vbeg = a0; sa.total = total; sa.dst = cx->d_snap;
-    sa.off = d_off; sa.nrec = (int64_t)nrec; sa.out_off = cx->d_find_off;
-    int64_t* part = reinterpret_cast<int64_t*>(cx->d_rec + 1);
-    sa.part = part; sa.cnt = cx->d_rec + 2 + tiles; sa.base = cx->d_rec + 2 + 2 * tiles;
-    launch_str_part(0, sa, part, tiles, s);
-    launch_str_stage(sa, tiles, s);
-    launch_chunk_scan(sa.cnt, const_cast<uint64_t*>(sa.base), tiles, s);
+    StrArgs sa;
+    rc = str_stage_text(cx, d_in, n, d_off, nrec, cx->d_find_off, s, &sa);
+    if (rc) return rc;
     // 3. a string that holds a '\n' would be several lines: the staged newlines are the strings' closing ones exactly when they are nrec
     uint64_t staged_nl = 0;
-    if (rec_status(cx, s, const_cast<uint64_t*>(sa.base) + tiles, &staged_nl) < 0) return TRRE_E_DEVICE;
+    if (str_staged_newlines(cx, sa, s, &staged_nl) < 0) return TRRE_E_DEVICE;
     if (staged_nl != nrec) return fail(TRRE_E_ARG, "error: a string holds a newline: it would be several lines, each with matches of its own");
     // 4. the one scan: markers and position bytes
     size_t m = 0;
-    const int rc = find_scan(p, st, cx->d_snap, (size_t)total, cx->d_framed, &m, s);
+    rc = find_scan(p, st, cx->d_snap, (size_t)total, cx->d_framed, &m, s);
     if (rc) return rc;                                      // (TRRE_E_DIVERGES: *n_matches stays 0)
     if ((int64_t)m < total) return fail(TRRE_E_DEVICE, "error: the framed text is shorter than the staged text (internal)");
     // 5. the markers per framed tile and before it; the table and the passes must agree before anything of the caller's is written
     const int64_t ftiles = ((int64_t)m + T - 1) / T;
-    HIP_TRY(rec_room(cx, 2 * ftiles + 2));
+    RecCarve c;                                             // (room as for 2 ftiles + 2 tiles; behind its part[0] the layout is this call's)
+    rc = rec_carve(cx, 2 * ftiles + 2, &c);
+    if (rc) return rc;
     SpanArgs pa{};
     pa.src = cx->d_framed; pa.total = (int64_t)m; pa.nrec = (int64_t)nrec; pa.tiles = ftiles;
-    pa.cnt = cx->d_rec + 2; pa.base = cx->d_rec + 2 + 3 * ftiles;
+    pa.cnt = reinterpret_cast<uint64_t*>(c.part) + 1; pa.base = pa.cnt + 3 * ftiles;
     launch_span_count(pa, s);
     uint64_t tot[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k) {
