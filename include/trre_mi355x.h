@@ -55,8 +55,8 @@ extern "C" {
                           * trre_find_device_strings and nothing else */
 #define TRRE_MODE_SPANS 8 /* where every match of every string starts and ends (finditer().span(), str.find, str.count): the positions
                            * of the same attempts, nothing of what they print.  NFT engine only; runs through
-                           * trre_span_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and stay
-                           * TRRE_E_ARG, as they were) */
+                           * trre_span_device_strings, trre_split_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums
+                           * of the modes above and stay TRRE_E_ARG, as they were) */
 
 /* return codes */
 #define TRRE_OK 0
@@ -324,6 +324,42 @@ int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
  * guided family's workspace once.  Synchronous with respect to `stream`; trre_last_scan_flags as for the strings call. */
 int trre_span_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* d_start,
                              int64_t* d_end, size_t span_cap, int64_t* d_list_off, size_t* n_matches, void* stream);
+
+/* Split strings: the same column of strings under a program compiled with TRRE_MODE_SPANS, cut at every match — a list of
+ * pieces per string (re.split, str.split, Arrow's split_pattern).  The definition rests on the spans of
+ * trre_span_device_strings: string i has bytes s and spans (s_0,e_0) .. (s_{c-1},e_{c-1}) relative to the string, ordered and
+ * disjoint (e_{k-1} <= s_k); its pieces are the c + 1 byte strings s[0:s_0], s[e_0:s_1], .., s[e_{c-1}:len(s)].  A string without
+ * a match is one piece, itself; an empty string is one empty piece; empty matches split ('x*' on "bb": '', 'b', 'b', '', as
+ * re.split); the search ends at a NUL, so the last piece keeps the NUL and everything behind it.  What the program prints plays
+ * no part.
+ *   d_out        cap bytes: the pieces, concatenated — the bytes of d_in outside every span, in order; *out_len = n minus the
+ *                matched bytes
+ *   d_piece_off  room for piece_cap + 1 entries: piece k is d_out[d_piece_off[k] .. d_piece_off[k + 1]), entry *n_pieces = *out_len
+ *   d_list_off   nrec + 1 entries: string i owns pieces d_list_off[i] .. d_list_off[i + 1] - 1; d_list_off[i] is the number of
+ *                matches in strings 0 .. i - 1, plus i; d_list_off[nrec] = *n_pieces = n_matches + nrec
+ * *n_pieces and *out_len may be null.  nrec == 0 is valid with n == 0: d_list_off[0] = 0, and d_piece_off[0] = 0 if d_piece_off
+ * is not null.  d_out may be null with cap == 0, d_piece_off with piece_cap == 0.  The offsets' check (TRRE_E_ARG, nothing
+ * written), a string that holds a '\n' (TRRE_E_ARG, found on the device before anything of the caller's is written) and a
+ * split-form scan in flight: as for trre_span_device_strings.  Any overlap among d_in, d_off, d_out, d_piece_off and
+ * d_list_off: TRRE_E_ARG — there is no in-place form.  Refused before the device is touched: a program not compiled with
+ * TRRE_MODE_SPANS (TRRE_E_ARG); TRRE_KERNEL_BACKTRACK forced through trre_set_kernel (TRRE_E_UNSUPPORTED); 2^55 strings or
+ * bytes, a piece_cap of 2^58 (TRRE_E_ARG).
+ *   TRRE_E_CAPACITY  exactly when *out_len > cap or *n_pieces > piece_cap: both sizes hold what is needed and d_list_off is
+ *                    valid; d_out and d_piece_off have not been written at all.  cap == 0 and piece_cap == 0 with both null is
+ *                    the size query, and a retry with room works.
+ *   TRRE_E_DIVERGES  *out_len = *n_pieces = 0; the arrays are unspecified; trre_last_error() holds the reference's message.
+ * How: the span call's passes up to its totals — the staged text, the one scan into the framed text (a position byte per
+ * staged byte, 0x01 in front of a match, 0x02 behind it), the three counters per 16 KiB framed tile and their sums.  0x01 and
+ * 0x02 alternate, so a position byte lies outside every match exactly when the number of markers before it is even: one more
+ * count pass gives the kept bytes per tile, their sum *out_len, and one compaction pass copies every kept byte from d_in to its
+ * place; the lane that owns 0x02 number j, behind l newlines, stores d_piece_off[j + 1 + l], the lane that owns newline number
+ * i, behind a matches, d_piece_off[a + i + 1] and d_list_off[i + 1] = a + i + 1.  Every byte and word is stored once.
+ * Device memory, kept by the (prog, device) until trre_free: the span call's — the staged text, n + nrec + 64 bytes; the framed
+ * text, n + nrec + 2 * n_matches + 64 bytes; 8 (nrec + 1) bytes of ranks; the general guided family's workspace once — with 72
+ * bytes per 16 KiB of the framed text in place of 48: the kept bytes per tile and before it.  Synchronous with respect to
+ * `stream`; trre_last_scan_flags as for the strings call. */
+int trre_split_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                              int64_t* d_piece_off, size_t piece_cap, int64_t* d_list_off, size_t* n_pieces, size_t* out_len, void* stream);
 
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */

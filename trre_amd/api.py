@@ -97,6 +97,7 @@ def lib():
         L.trre_match_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_find_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_span_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, ctypes.POINTER(sz), vp]
+        L.trre_split_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -161,7 +162,8 @@ class Program:
         """mode "scan" (default), "match" (`trre -m`: whole-line matches only, NFT engine), "scan_all" (`trre -a`) or
         "match_all" (`trre -ma`): generator modes, every accepting path prints (NFT engine), or "find": every match of every
         string as a list per string (find_strings / find_list, NFT engine), or "spans": where every match of every string starts
-        and ends (span_strings / span_list / count_strings, NFT engine)"""
+        and ends (span_strings / span_list / count_strings, NFT engine) and the pieces between the matches (split_strings /
+        split_list)"""
         self.pattern = _bytes(pattern)
         self.engine = _ENGINES[engine]
         self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL,
@@ -461,6 +463,39 @@ class Program:
         starts, ends, list_off = self.span_strings(values, offsets)
         st, en, lo = starts.cpu().numpy().tolist(), ends.cpu().numpy().tolist(), list_off.cpu().numpy().tolist()
         return [[(st[j] - int(off[i]), en[j] - int(off[i])) for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
+
+    def split_strings(self, values, offsets, stream=None):
+        """Split strings (trre_split_device_strings; a program compiled with mode="spans"): values and offsets as for
+        scan_strings, no string holding a b"\\n".  Every string is cut at every match, as re.split cuts it.  Returns (out,
+        piece_offsets, list_offsets): string i's pieces are numbers list_offsets[i] .. list_offsets[i + 1] - 1 (one more than
+        its matches), and piece k is out[piece_offsets[k]:piece_offsets[k + 1]].  Two calls: the size query, then the one that
+        fills buffers of exactly that size."""
+        import torch
+        n, nrec, s = _column(values, offsets, stream)
+        list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        m, k = ctypes.c_size_t(), ctypes.c_size_t()
+
+        def call(o, cap, po, pcap):
+            return lib().trre_split_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, o, cap, po, pcap,
+                                                   list_off.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
+        with torch.cuda.device(values.device):
+            rc = call(None, 0, None, 0)
+            if rc not in (0, E_CAPACITY):
+                _check(rc)
+            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
+            piece_off = torch.zeros(k.value + 1, dtype=torch.int64, device=values.device)
+            if rc == E_CAPACITY:
+                _check(call(out.data_ptr(), m.value, piece_off.data_ptr(), k.value))
+        return out[:m.value], piece_off, list_off
+
+    def split_list(self, records, device=0):
+        """list of bytes in -> per string the list of its pieces (bytes), as re.split gives them (through split_strings)"""
+        recs, off, values, offsets = _pack(records, device)
+        out, piece_off, list_off = self.split_strings(values, offsets)
+        blob = out.cpu().numpy().tobytes()
+        po = piece_off.cpu().numpy().tolist()
+        lo = list_off.cpu().numpy().tolist()
+        return [[blob[po[j]:po[j + 1]] for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
 
     @staticmethod
     def _map_list(records, device, scan):

@@ -15,6 +15,7 @@ struct RecArgs;
 struct StrArgs;
 struct MatchArgs;
 struct SpanArgs;
+struct SplitArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -112,6 +113,10 @@ void launch_find_unframe(const StrArgs& a, int64_t tiles, void* stream);
 // the list offsets (a.tiles tiles each)
 void launch_span_count(const SpanArgs& a, void* stream);
 void launch_span_emit(const SpanArgs& a, void* stream);
+// split strings (records_block.hpp), behind launch_span_count and its scans: the kept bytes per framed tile (a.kcnt), then — behind
+// their exclusive scan — the pieces' bytes, the piece offsets and the list offsets
+void launch_split_count(const SplitArgs& a, void* stream);
+void launch_split_emit(const SplitArgs& a, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

@@ -740,4 +740,116 @@ TRRE_HD void span_emit_pieces(const SpanArgs& a, int64_t b, int tid, const uint1
     }
 }
 
+// ---- split strings (trre_split_device_strings) -----------------------------------------------------------------------------
+// The pieces of a column split at every match are the bytes OUTSIDE every span, in order: a stream compaction over the framed
+// text of the span call.  A and B alternate strictly, so with a, b, l the A, B, '\n' before framed position q, the DEPTH at q
+// is a - b (0 or 1), the parity of a + b; a position byte is KEPT exactly when its depth is 0; a '\n' is always at depth 0 and
+// is never kept; a tile, or a 64-byte piece of one, may lie wholly inside one match and hold no marker at all.  With kp the
+// kept bytes before q:
+//     kept byte at q       out[kp] = in[q - a - b - l]
+//     B number j at q      piece_off[j + 1 + l] = kp           (the piece behind match j starts here)
+//     '\n' number i at q   piece_off[a + i + 1] = kp,  list_off[i + 1] = a + i + 1     (i = nrec - 1: the terminator, out_len)
+// piece_off[0] = list_off[0] = 0.  The passes, behind k_span_count and its three scans (base[3][tiles + 1]):
+//   k_split_count  the kept bytes per framed tile: kcnt[tiles] — the tile's depth on entry is base[0][b] - base[1][b], a thread
+//                  segment's that plus the markers before it in the tile (a workgroup scan);  k_chunk_scan: kbase[tiles + 1];
+//                  the total is out_len, read back with the other totals
+//   k_split_emit   k_span_emit's three mark images, a fourth for the kept bits and its workgroup scan; then a wave takes 64
+//                  framed bytes at a time, four 64-bit words per piece
+// Who writes which byte and word: entry 0 of both arrays thread 0 of tile 0; every output byte the lane that owns its kept
+// position byte (adjacent kept lanes store adjacent bytes); every other word the lane that owns its B or '\n', once.  An A lane
+// stores nothing.  lists_only: out and piece_off are not stored at all (TRRE_E_CAPACITY, the size query).
+struct SplitArgs {
+    const uint8_t* src;     // the framed text: 16-byte aligned, whole vectors readable behind its end
+    int64_t total;          // framed length
+    const uint8_t* in;      // the caller's d_in
+    int64_t n;
+    uint8_t* out;           // [out_len]
+    int64_t out_len;
+    int64_t* piece_off;     // [n_piece + 1]
+    int64_t n_piece;
+    int64_t* list_off;      // [nrec + 1]
+    int64_t nrec;
+    int64_t tiles;
+    const uint64_t* base;   // [3][tiles + 1] A, B, '\n' before every tile (k_span_count, k_chunk_scan)
+    uint64_t* kcnt;         // [tiles] kept bytes per tile
+    const uint64_t* kbase;  // [tiles + 1] their exclusive scan
+    uint32_t lists_only;
+};
+
+// bit k: an odd number of the 16 bits of m below bit k are set
+TRRE_HD uint32_t split_odd_below16(uint32_t m) {
+    m ^= m << 1; m ^= m << 2; m ^= m << 4; m ^= m << 8;
+    return (m << 1) & 0xffffu;
+}
+// the tile's marks, as k_span_emit takes them
+template <class G>
+TRRE_HD void split_mark_vecs(const SplitArgs& a, int64_t b, int tid, uint16_t* bits) {
+    SpanArgs sp{};
+    sp.src = a.src; sp.total = a.total;
+    uint32_t c[3] = {0u, 0u, 0u};
+    span_mark_vecs<G>(sp, b, tid, bits, c);
+}
+// the kept bits of the thread's rank segment, vectors [tid * VECS, tid * VECS + VECS) (pre_ab: A | B << 16 before the segment in
+// the tile); kept: [NVEC] 16-bit masks, or null (k_split_count).  Returns the segment's kept bytes
+template <class G>
+TRRE_HD uint32_t split_seg_kept(const SplitArgs& a, int64_t b, int tid, const uint16_t* bits, uint32_t pre_ab, uint16_t* kept) {
+    uint32_t d = (uint32_t)(a.base[b] + a.base[a.tiles + 1 + b] + (pre_ab & 0xffffu) + (pre_ab >> 16)) & 1u;
+    uint32_t c = 0;
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        const int64_t v = b * G::TILE + 16 * (int64_t)q;
+        const uint32_t mk = (uint32_t)bits[q] | bits[G::NVEC + q], nl = bits[2 * G::NVEC + q];
+        const uint32_t ok = v < a.total ? rec_valid16(v, 0, a.total) : 0u;
+        const uint32_t kp = ~(split_odd_below16(mk) ^ (0u - d)) & ~mk & ~nl & ok;
+        if (kept) kept[q] = (uint16_t)kp;
+        c += rec_popc(kp);
+        d ^= rec_popc(mk) & 1u;
+    }
+    return c;
+}
+// kept bytes before each of the thread's segment vectors (pre_k: before the segment)
+template <class G>
+TRRE_HD void split_fill_pv(const uint16_t* kept, uint32_t pre_k, int tid, uint32_t* pv_k) {
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        pv_k[q] = pre_k;
+        pre_k += rec_popc(kept[q]);
+    }
+}
+// k_split_emit, behind the barrier that completes the four images and the three pv: the tile's bytes and words
+template <class G>
+TRRE_HD void split_emit_pieces(const SplitArgs& a, int64_t b, int tid, const uint16_t* bits, const uint16_t* kept, const uint32_t* pv_ab,
+                               const uint32_t* pv_nl, const uint32_t* pv_k) {
+    static_assert(G::THREADS % 64 == 0 && G::NVEC % 4 == 0, "a wave takes 64-byte pieces of the tile");
+    constexpr int kPieces = G::NVEC / 4, kWaves = G::THREADS / 64;
+    const int lane = tid & 63;
+    const int64_t s0 = b * G::TILE;
+    const int64_t a0 = (int64_t)a.base[b], b0 = (int64_t)a.base[a.tiles + 1 + b], l0 = (int64_t)a.base[2 * (a.tiles + 1) + b];
+    const int64_t k0 = (int64_t)a.kbase[b];
+    if (b == 0 && tid == 0) {
+        a.list_off[0] = 0;
+        if (!a.lists_only) a.piece_off[0] = 0;
+    }
+    for (int k = tid >> 6; k < kPieces; k += kWaves) {
+        const uint64_t wa = span_word(bits, k), wb = span_word(bits + G::NVEC, k), wl = span_word(bits + 2 * G::NVEC, k);
+        const uint64_t wk = span_word(kept, k);
+        if (!(((a.lists_only ? wl : wb | wl | wk) >> lane) & 1u)) continue;
+        const uint64_t below = (1ull << lane) - 1ull;
+        const int64_t na = a0 + (int64_t)(pv_ab[4 * k] & 0xffffu) + (int64_t)match_popc64(wa & below);
+        const int64_t nb = b0 + (int64_t)(pv_ab[4 * k] >> 16) + (int64_t)match_popc64(wb & below);
+        const int64_t nl = l0 + (int64_t)pv_nl[4 * k] + (int64_t)match_popc64(wl & below);
+        const int64_t kp = k0 + (int64_t)pv_k[4 * k] + (int64_t)match_popc64(wk & below);
+        // (never beyond: the four totals were checked against n, the pieces and nrec before this pass)
+        if ((wk >> lane) & 1u) {
+            const int64_t at = s0 + 64 * (int64_t)k + lane - na - nb - nl;
+            if (kp < a.out_len && at >= 0 && at < a.n) a.out[kp] = a.in[at];
+        } else if ((wb >> lane) & 1u) {
+            if (nb + 1 + nl <= a.n_piece) a.piece_off[nb + 1 + nl] = kp;
+        } else if (nl < a.nrec) {
+            a.list_off[nl + 1] = na + nl + 1;
+            if (!a.lists_only && na + nl + 1 <= a.n_piece) a.piece_off[na + nl + 1] = kp;
+        }
+    }
+}
+
 }  // namespace trre

@@ -659,7 +659,7 @@ constexpr uint64_t kGuardBudget = 1ull << 23;              // search steps per l
 constexpr uint64_t kGuardCallBudget = 1ull << 35;
 constexpr const char* kStackMsg = "error: stack max capacity reached";
 constexpr const char* kFindOnlyMsg = "error: a program compiled with TRRE_MODE_FIND runs through trre_find_device_strings only";
-constexpr const char* kSpansOnlyMsg = "error: a program compiled with TRRE_MODE_SPANS runs through trre_span_device_strings only";
+constexpr const char* kSpansOnlyMsg = "error: a program compiled with TRRE_MODE_SPANS runs through trre_span_device_strings and trre_split_device_strings only";
 constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
 // a program that one call alone runs: that call's name for every other call's refusal (null: any scan call may run it)
 const char* own_call_only(const trre_prog& p) {
@@ -2771,21 +2771,34 @@ int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     return find_on(p, st, stm, d_in, n, d_off, nrec, d_out, cap, d_match_off, match_cap, d_list_off, n_matches, out_len, static_cast<hipStream_t>(stream));
 }
 
-// ---- match spans (records_block.hpp) ---------------------------------------------------------------------------------------
+// ---- match spans and split strings (records_block.hpp) ---------------------------------------------------------------------
 // The context holds the staged text (d_snap), the staging passes' ranks (d_find_off: nobody reads them here, k_str_stage writes
-// them), the framed text (d_framed) and, in d_rec behind the status word, cnt [3][tiles] and base [3][tiles + 1]
-static int span_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* d_start,
-                   int64_t* d_end, size_t span_cap, int64_t* d_list_off, size_t* n_matches, hipStream_t s) {
+// them), the framed text (d_framed) and, in d_rec behind the status word, cnt [3][tiles] and base [3][tiles + 1] — for the split
+// call kcnt [tiles] and kbase [tiles + 1] behind them
+struct SpanMarks {
+    bool empty;             // nrec == 0: the offsets passed and nothing else ran
+    trre::SpanArgs pa;      // src, total, nrec, tiles, cnt, base
+    size_t found;           // matches
+    uint64_t* kcnt;         // (kept) the kept bytes per framed tile,
+    uint64_t* kbase;        // their exclusive scan,
+    uint64_t kept;          // and their total
+};
+
+// What the span call and the split call share, up to the one read-back before anything of the caller's is written: the offsets'
+// check, the staged text, its newline check, the one scan into d_framed, k_span_count with its three scans and the totals'
+// check.  kept (the split call): k_split_count and its scan go in front of that read-back, and their total comes with the others.
+static int span_marks(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, bool kept, hipStream_t s,
+                      SpanMarks* out) {
     using namespace trre;
     ScanCtx* cx = &st->ctx;
     const int64_t T = str_tile_bytes();
     const int64_t total = (int64_t)(n + nrec);                     // the staged text
+    *out = SpanMarks{};
     // 1. the offsets, on the device: nothing is written before they pass
     int rc = rec_check_offsets(cx, (total + T - 1) / T, d_off, nrec, n, s);
     if (rc) return rc;
     if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        out->empty = true;
         return TRRE_OK;
     }
     // 2. the staged text, as for the strings call; the ranks its stage pass leaves go into the library's own array
@@ -2800,14 +2813,14 @@ static int span_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n,
     // 4. the one scan: markers and position bytes
     size_t m = 0;
     rc = find_scan(p, st, cx->d_snap, (size_t)total, cx->d_framed, &m, s);
-    if (rc) return rc;                                      // (TRRE_E_DIVERGES: *n_matches stays 0)
+    if (rc) return rc;                                      // (TRRE_E_DIVERGES: the caller's sizes stay 0)
     if ((int64_t)m < total) return fail(TRRE_E_DEVICE, "error: the framed text is shorter than the staged text (internal)");
     // 5. the markers per framed tile and before it; the table and the passes must agree before anything of the caller's is written
     const int64_t ftiles = ((int64_t)m + T - 1) / T;
-    RecCarve c;                                             // (room as for 2 ftiles + 2 tiles; behind its part[0] the layout is this call's)
-    rc = rec_carve(cx, 2 * ftiles + 2, &c);
+    RecCarve c;                                             // (room as for 2 ftiles + 2 tiles, 3 ftiles + 2 with the kept bytes; behind its part[0] the layout is this call's)
+    rc = rec_carve(cx, (kept ? 3 : 2) * ftiles + 2, &c);
     if (rc) return rc;
-    SpanArgs pa{};
+    SpanArgs& pa = out->pa;
     pa.src = cx->d_framed; pa.total = (int64_t)m; pa.nrec = (int64_t)nrec; pa.tiles = ftiles;
     pa.cnt = reinterpret_cast<uint64_t*>(c.part) + 1; pa.base = pa.cnt + 3 * ftiles;
     launch_span_count(pa, s);
@@ -2817,16 +2830,39 @@ static int span_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n,
         launch_chunk_scan(pa.cnt + k * ftiles, base, ftiles, s);
         HIP_TRY(hipMemcpyAsync(&tot[k], base + ftiles, 8, hipMemcpyDeviceToHost, s));
     }
+    if (kept) {
+        out->kcnt = const_cast<uint64_t*>(pa.base) + 3 * (ftiles + 1); out->kbase = out->kcnt + ftiles;
+        SplitArgs ka{};
+        ka.src = pa.src; ka.total = pa.total; ka.tiles = ftiles; ka.base = pa.base; ka.kcnt = out->kcnt;
+        launch_split_count(ka, s);
+        launch_chunk_scan(out->kcnt, out->kbase, ftiles, s);
+        HIP_TRY(hipMemcpyAsync(&out->kept, out->kbase + ftiles, 8, hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
-    if (tot[0] != tot[1] || tot[2] != nrec || m != (size_t)total + 2 * tot[0])
+    if (tot[0] != tot[1] || tot[2] != nrec || m != (size_t)total + 2 * tot[0] || out->kept > n)
         return fail(TRRE_E_DEVICE, "error: the markers of the framed text do not add up (internal)");
-    const size_t found = (size_t)tot[0];
+    out->found = (size_t)tot[0];
+    return TRRE_OK;
+}
+
+static int span_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t* d_start,
+                   int64_t* d_end, size_t span_cap, int64_t* d_list_off, size_t* n_matches, hipStream_t s) {
+    SpanMarks mk;
+    const int rc = span_marks(p, st, d_in, n, d_off, nrec, false, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    const size_t found = mk.found;
     if (n_matches) *n_matches = found;
     // 6. the spans and the list offsets — the list offsets alone when the spans do not fit
     const bool over = found > span_cap;
+    trre::SpanArgs& pa = mk.pa;
     pa.start = d_start; pa.end = d_end; pa.list_off = d_list_off; pa.n_match = over ? 0 : (int64_t)found; pa.lists_only = over ? 1u : 0u;
-    launch_span_emit(pa, s);
+    trre::launch_span_emit(pa, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return over ? fail(TRRE_E_CAPACITY, "error: output buffer too small") : TRRE_OK;
@@ -2853,6 +2889,57 @@ int trre_span_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     std::lock_guard<std::mutex> lock(st->mu);
     if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
     return span_on(p, st, d_in, n, d_off, nrec, d_start, d_end, span_cap, d_list_off, n_matches, static_cast<hipStream_t>(stream));
+}
+
+// the pieces between the matches: steps 1 - 5 are the span call's, with the kept bytes counted in front of the read-back
+static int split_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                    int64_t* d_piece_off, size_t piece_cap, int64_t* d_list_off, size_t* n_pieces, size_t* out_len, hipStream_t s) {
+    SpanMarks mk;
+    const int rc = span_marks(p, st, d_in, n, d_off, nrec, true, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
+        if (d_piece_off) HIP_TRY(hipMemsetAsync(d_piece_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    const size_t pieces = mk.found + nrec, kept = (size_t)mk.kept;
+    if (n_pieces) *n_pieces = pieces;
+    if (out_len) *out_len = kept;
+    // 6. the pieces, where each starts and the list offsets — the list offsets alone when either does not fit
+    const bool over = kept > cap || pieces > piece_cap;
+    trre::SplitArgs a{};
+    a.src = mk.pa.src; a.total = mk.pa.total; a.in = d_in; a.n = (int64_t)n; a.list_off = d_list_off; a.nrec = (int64_t)nrec;
+    a.tiles = mk.pa.tiles; a.base = mk.pa.base; a.kcnt = mk.kcnt; a.kbase = mk.kbase; a.lists_only = over ? 1u : 0u;
+    if (!over) { a.out = d_out; a.out_len = (int64_t)kept; a.piece_off = d_piece_off; a.n_piece = (int64_t)pieces; }
+    trre::launch_split_emit(a, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return over ? fail(TRRE_E_CAPACITY, "error: output buffer too small") : TRRE_OK;
+}
+
+int trre_split_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
+                              int64_t* d_piece_off, size_t piece_cap, int64_t* d_list_off, size_t* n_pieces, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_pieces) *n_pieces = 0;
+    if (!p || !d_off || !d_list_off || (n && !d_in) || (cap && !d_out) || (piece_cap && !d_piece_off)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: split strings take a program compiled with TRRE_MODE_SPANS");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || piece_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    const size_t ob = (nrec + 1) * 8, pb = d_piece_off ? (piece_cap + 1) * 8 : 0, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the pieces are not made in place)");
+    if (ranges_overlap(d_off, ob, d_list_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cb) ||
+        ranges_overlap(d_list_off, ob, d_in, n) || ranges_overlap(d_list_off, ob, d_out, cb) || ranges_overlap(d_piece_off, pb, d_in, n) ||
+        ranges_overlap(d_piece_off, pb, d_out, cb) || ranges_overlap(d_piece_off, pb, d_off, ob) || ranges_overlap(d_piece_off, pb, d_list_off, ob))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    DeviceState* st;
+    const int rc = current_state(p, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return split_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_piece_off, piece_cap, d_list_off, n_pieces, out_len, static_cast<hipStream_t>(stream));
 }
 
 namespace {

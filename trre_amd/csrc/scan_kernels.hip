@@ -1828,6 +1828,66 @@ __global__ __launch_bounds__(SG::THREADS) void k_span_emit(SpanArgs a) {
     span_emit_pieces<SG>(a, b, tid, bits, pv_ab, pv_nl);
 }
 
+// ---- split strings (records_block.hpp; runtime.cpp: trre_split_device_strings) ---------------------------------------------
+// The kept bytes per framed tile.  The mark images are written by all threads and read across them (a thread's rank segment is
+// not the vectors it loaded): a barrier stands behind split_mark_vecs; the scan's own barriers stand between pre_ab and its
+// readers and between its use of wtot and the sums'.
+__global__ __launch_bounds__(SG::THREADS) void k_split_count(SplitArgs a) {
+    __shared__ uint16_t bits[3 * SG::NVEC];
+    __shared__ uint32_t pre_ab[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    split_mark_vecs<SG>(a, b, tid, bits);
+    __syncthreads();
+    uint32_t ab, nl;
+    span_seg_count<SG>(bits, tid, ab, nl);
+    rec_block_scan(ab, pre_ab, wtot);
+    const uint64_t s = wave_sum(split_seg_kept<SG>(a, b, tid, bits, pre_ab[tid], nullptr));
+    if ((tid & (kWave - 1)) == 0) wtot[tid / kWave] = (uint32_t)s;
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t t = 0;
+        for (int k = 0; k < SG::THREADS / kWave; ++k) t += wtot[k];
+        a.kcnt[b] = t;
+    }
+}
+
+// The pieces' bytes, where each piece starts and the list offsets.  Barriers: behind split_mark_vecs (the images are read across
+// threads); the three scans' own; the kept image is written and read by its segment's thread until the last barrier, which
+// completes kept and the three pv for split_emit_pieces — it reads the words and prefixes of pieces other threads filled.
+__global__ __launch_bounds__(SG::THREADS) void k_split_emit(SplitArgs a) {
+    __shared__ uint16_t bits[3 * SG::NVEC];
+    __shared__ uint16_t kept[SG::NVEC];
+    __shared__ uint32_t pv_ab[SG::NVEC];
+    __shared__ uint32_t pv_nl[SG::NVEC];
+    __shared__ uint32_t pv_k[SG::NVEC];
+    __shared__ uint32_t pre_ab[SG::THREADS];
+    __shared__ uint32_t pre_nl[SG::THREADS];
+    __shared__ uint32_t pre_k[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    split_mark_vecs<SG>(a, b, tid, bits);
+    __syncthreads();
+    uint32_t ab, nl;
+    span_seg_count<SG>(bits, tid, ab, nl);
+    rec_block_scan(ab, pre_ab, wtot);
+    rec_block_scan(nl, pre_nl, wtot);
+    span_fill_pv<SG>(bits, pre_ab[tid], pre_nl[tid], tid, pv_ab, pv_nl);
+    rec_block_scan(split_seg_kept<SG>(a, b, tid, bits, pre_ab[tid], kept), pre_k, wtot);
+    split_fill_pv<SG>(kept, pre_k[tid], tid, pv_k);
+    __syncthreads();
+    split_emit_pieces<SG>(a, b, tid, bits, kept, pv_ab, pv_nl, pv_k);
+}
+
+void launch_split_count(const SplitArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_split_count, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_split_emit(const SplitArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_split_emit, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+
 void launch_span_count(const SpanArgs& a, void* stream) {
     hipLaunchKernelGGL(k_span_count, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
 }
