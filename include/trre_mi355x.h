@@ -55,8 +55,8 @@ extern "C" {
                           * trre_find_device_strings and nothing else */
 #define TRRE_MODE_SPANS 8 /* where every match of every string starts and ends (finditer().span(), str.find, str.count): the positions
                            * of the same attempts, nothing of what they print.  NFT engine only; runs through
-                           * trre_span_device_strings, trre_split_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums
-                           * of the modes above and stay TRRE_E_ARG, as they were) */
+                           * trre_span_device_strings, trre_split_device_strings, trre_filter_device_strings and nothing else.  (8,
+                           * not 5: 5, 6 and 7 read as sums of the modes above and stay TRRE_E_ARG, as they were) */
 
 /* return codes */
 #define TRRE_OK 0
@@ -360,6 +360,43 @@ int trre_span_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
  * `stream`; trre_last_scan_flags as for the strings call. */
 int trre_split_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out, size_t cap,
                               int64_t* d_piece_off, size_t piece_cap, int64_t* d_list_off, size_t* n_pieces, size_t* out_len, void* stream);
+
+/* Filtered strings: the same column of strings under a program compiled with TRRE_MODE_SPANS, with the strings the pattern
+ * matches somewhere kept and the rest dropped — s[s.str.contains(p)], grep / grep -v on a column, Arrow's filter over
+ * match_substring_regex — and the rows that were kept, for the sibling columns.  The definition rests on the spans of
+ * trre_span_device_strings: string i is kept exactly when it has at least one match there (d_list_off[i + 1] - d_list_off[i] > 0);
+ * with TRRE_FILTER_INVERT in `flags`, exactly when it has none.  Empty matches count ('x*' keeps every string, the empty one
+ * included); the search ends at a NUL ('(cat|dog)' drops "\0cat" and keeps "a cat\0dog"); what the program prints plays no
+ * part.  A kept string is copied whole, a NUL and everything behind it included.
+ *   d_out      cap bytes: the kept strings, concatenated in input order; *out_len is their total
+ *   d_out_off  room for row_cap + 1 entries: kept string r is d_out[d_out_off[r] .. d_out_off[r + 1]); d_out_off[0] = 0,
+ *              d_out_off[*n_kept] = *out_len
+ *   d_rows     room for row_cap entries: d_rows[r] is the index in the input column of kept string r; strictly increasing
+ * *n_kept and *out_len may be null.  d_out may be null only with cap == 0, d_out_off and d_rows only with row_cap == 0; all
+ * three null with both capacities 0 is the size query.  nrec == 0 is valid with n == 0: TRRE_OK, and d_out_off[0] = 0 if
+ * d_out_off is not null; the same when nrec > 0 and nothing is kept (*n_kept = *out_len = 0).  The offsets' check (TRRE_E_ARG,
+ * nothing written), a string that holds a '\n' (TRRE_E_ARG, found on the device before anything of the caller's is written) and
+ * a split-form scan in flight: as for trre_span_device_strings.  Any overlap among d_in, d_off, d_out, d_out_off and d_rows:
+ * TRRE_E_ARG — there is no in-place form.  Refused before the device is touched: a null argument, a bit of `flags` other than
+ * TRRE_FILTER_INVERT, a program not compiled with TRRE_MODE_SPANS (TRRE_E_ARG); TRRE_KERNEL_BACKTRACK forced through
+ * trre_set_kernel (TRRE_E_UNSUPPORTED); 2^55 strings or bytes, a row_cap of 2^58 (TRRE_E_ARG).
+ *   TRRE_E_CAPACITY  exactly when *out_len > cap or *n_kept > row_cap: both sizes hold what is needed; d_out, d_out_off and
+ *                    d_rows have not been written at all, and a retry with that room succeeds.
+ *   TRRE_E_DIVERGES  *n_kept = *out_len = 0; the arrays are unspecified; trre_last_error() holds the reference's message.
+ * How: the span call's passes with its list offsets, and nothing else of it, stored into an array of the library's own.  Then,
+ * over 16 KiB tiles of the INPUT (aligned to 16 bytes by address): the first string that ends in every tile (a binary search
+ * per tile); per tile the kept strings that end in it and its kept bytes, from the offsets and the list offsets alone; their
+ * two exclusive sums, whose totals are *n_kept and *out_len, read back in one synchronisation; and one compaction pass that
+ * takes the tile into LDS as whole vectors, marks the kept bytes with a bit each (start and end toggles of the kept strings
+ * and a prefix XOR) and writes the tile's contiguous part of d_out as whole aligned 16-byte vectors, bytes only at the two
+ * ends it shares with its neighbours.  The thread that owns kept string r stores d_rows[r] and d_out_off[r + 1].  Every byte
+ * and word is stored once.
+ * Device memory, kept by the (prog, device) until trre_free: the span call's, and 8 (nrec + 1) bytes of list offsets and 48
+ * bytes per 16 KiB of the input.  Synchronous with respect to `stream`; trre_last_scan_flags as for the strings call. */
+#define TRRE_FILTER_INVERT 1u   /* keep the strings WITHOUT a match (grep -v) */
+int trre_filter_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint32_t flags,
+                               uint8_t* d_out, size_t cap, int64_t* d_out_off, int64_t* d_rows, size_t row_cap, size_t* n_kept,
+                               size_t* out_len, void* stream);
 
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */

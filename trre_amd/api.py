@@ -34,6 +34,8 @@ FLAG_LENGTH_PRESERVING, FLAG_MEMORYLESS, FLAG_NO_OVERRUN = 1, 2, 4
 E_SYNTAX, E_UNDEFINED, E_EPS_CYCLE, E_TOO_BIG, E_UNSUPPORTED = -1, -2, -3, -4, -5
 E_DEVICE, E_ARG, E_DIVERGES, E_CAPACITY = -6, -7, -8, -9
 
+FILTER_INVERT = 1
+
 
 class TrreError(RuntimeError):
     """A failed library call; .code is the TRRE_E_* value, .message the
@@ -98,6 +100,7 @@ def lib():
         L.trre_find_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_span_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, ctypes.POINTER(sz), vp]
         L.trre_split_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_filter_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -163,7 +166,7 @@ class Program:
         "match_all" (`trre -ma`): generator modes, every accepting path prints (NFT engine), or "find": every match of every
         string as a list per string (find_strings / find_list, NFT engine), or "spans": where every match of every string starts
         and ends (span_strings / span_list / count_strings, NFT engine) and the pieces between the matches (split_strings /
-        split_list)"""
+        split_list) and the strings with a match or without one (filter_strings / filter_list)"""
         self.pattern = _bytes(pattern)
         self.engine = _ENGINES[engine]
         self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL,
@@ -496,6 +499,40 @@ class Program:
         po = piece_off.cpu().numpy().tolist()
         lo = list_off.cpu().numpy().tolist()
         return [[blob[po[j]:po[j + 1]] for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
+
+    def filter_strings(self, values, offsets, invert=False, stream=None):
+        """Filtered strings (trre_filter_device_strings; a program compiled with mode="spans"): values and offsets as for
+        scan_strings, no string holding a b"\\n".  The strings with at least one match are kept whole and the rest dropped, as
+        s[s.str.contains(p)]; with invert=True the strings without a match are kept (grep -v).  Returns (out, out_offsets,
+        rows): kept string r is out[out_offsets[r]:out_offsets[r + 1]] and was string rows[r] of the column (int64, strictly
+        increasing: the index that filters the sibling columns).  Two calls: the size query, then the one that fills buffers of
+        exactly that size."""
+        import torch
+        n, nrec, s = _column(values, offsets, stream)
+        flags = FILTER_INVERT if invert else 0
+        m, k = ctypes.c_size_t(), ctypes.c_size_t()
+
+        def call(o, cap, oo, rows, rcap):
+            return lib().trre_filter_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, flags, o, cap, oo, rows,
+                                                    rcap, ctypes.byref(k), ctypes.byref(m), s)
+        with torch.cuda.device(values.device):
+            rc = call(None, 0, None, None, 0)
+            if rc not in (0, E_CAPACITY):
+                _check(rc)
+            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
+            out_off = torch.zeros(k.value + 1, dtype=torch.int64, device=values.device)
+            rows = torch.empty(k.value, dtype=torch.int64, device=values.device)
+            if rc == E_CAPACITY:
+                _check(call(out.data_ptr(), m.value, out_off.data_ptr(), rows.data_ptr(), k.value))
+        return out[:m.value], out_off, rows
+
+    def filter_list(self, records, invert=False, device=0):
+        """list of bytes in -> (the kept strings, their indices in the list) (through filter_strings)"""
+        recs, off, values, offsets = _pack(records, device)
+        out, out_off, rows = self.filter_strings(values, offsets, invert=invert)
+        blob = out.cpu().numpy().tobytes()
+        o = out_off.cpu().numpy().tolist()
+        return [blob[o[r]:o[r + 1]] for r in range(len(o) - 1)], rows.cpu().numpy().tolist()
 
     @staticmethod
     def _map_list(records, device, scan):

@@ -16,6 +16,7 @@ struct StrArgs;
 struct MatchArgs;
 struct SpanArgs;
 struct SplitArgs;
+struct FilterArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -117,6 +118,11 @@ void launch_span_emit(const SpanArgs& a, void* stream);
 // their exclusive scan — the pieces' bytes, the piece offsets and the list offsets
 void launch_split_count(const SplitArgs& a, void* stream);
 void launch_split_emit(const SplitArgs& a, void* stream);
+// filtered strings (records_block.hpp), behind launch_span_emit's list offsets: the first string of every tile of the input
+// (a.part) and the kept strings and bytes per tile (a.cnt), then — behind their two exclusive scans — the kept strings' bytes,
+// their offsets and their rows (a.tiles tiles of str_tile_bytes() each)
+void launch_filter_count(const FilterArgs& a, void* stream);
+void launch_filter_emit(const FilterArgs& a, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

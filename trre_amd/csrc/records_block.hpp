@@ -852,4 +852,216 @@ TRRE_HD void split_emit_pieces(const SplitArgs& a, int64_t b, int tid, const uin
     }
 }
 
+// ---- filtered strings (trre_filter_device_strings) -------------------------------------------------------------------------
+// The strings with a match (without one: invert), whole, in order, and which rows they were: a stream compaction of whole
+// strings.  The verdict is the span call's: kept(i) = (list_off[i + 1] > list_off[i]) != invert, from k_span_emit's list offsets
+// in an array of the library's own.  The tiles are over the INPUT's v-space (v = position + vbeg, vbeg = d_in's address mod 16),
+// so a tile's source vectors are aligned; with no byte at all (every string empty) there is still one tile.  The passes:
+//   k_filter_part   part[b] = the first string whose end lies in tile b or after it (rec_part_in's partition: the empty string
+//                   at position 0 belongs to tile 0)
+//   k_filter_count  per tile the kept strings among those that END in it, and its kept bytes: the overlap with the tile of every
+//                   kept string that ends in it, and of the one string that covers the tile's end (string part[b + 1]).  Offsets
+//                   and list offsets only; the text is not read.  cnt[2][tiles];  k_chunk_scan twice: base[2][tiles + 1]; the
+//                   totals are n_kept and out_len, read back and checked before anything of the caller's is stored
+//   k_filter_emit   the tile's source vectors into LDS; a bit per byte that TOGGLES where a kept string starts and where it ends
+//                   (XOR: the end of a kept string and the start of the next kept one fall on one position and cancel, as the
+//                   two toggles of an empty kept string do); the prefix XOR of the toggles is the kept image; its workgroup scan
+//                   gives every byte its rank.  The tile's kept bytes go to out[kbase[b] .. kbase[b + 1]), output-parallel: the
+//                   whole 16-byte vectors of the destination ADDRESS (as k_str_unframe's StrOut) are aligned vector stores, the
+//                   ragged first and last ones, which the neighbouring tiles share, byte stores.
+// Strings to threads: the tile's strings [i0, i1) in THREADS consecutive runs of ceil((i1 - i0) / THREADS), so a thread's rank in
+// the tile is one workgroup scan away however many strings end in the tile.  No thread loops over the bytes of a string.
+// Who writes which byte and word: out_off[0] thread 0 of tile 0; rows[r] and out_off[r + 1] the thread that owns kept string r,
+// in the tile the string ends in; every output byte the thread that owns its destination vector, once.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TRRE_REC_LDS_XOR(p, v) atomicXor((p), (v))
+#else
+#define TRRE_REC_LDS_XOR(p, v) (*(p) ^= (v))
+#endif
+
+struct FilterArgs {
+    const uint8_t* in_v0;   // the caller's d_in - vbeg: 16-byte aligned
+    int64_t vbeg, n;        // d_in's address mod 16; its bytes
+    const int64_t* off;     // [nrec + 1] the caller's offsets
+    const int64_t* loff;    // [nrec + 1] the span call's list offsets
+    int64_t nrec;
+    uint32_t invert;
+    int64_t tiles;
+    int64_t* part;          // [tiles + 1] first string of each tile
+    uint64_t* cnt;          // [2][tiles] kept strings, kept bytes per tile
+    const uint64_t* base;   // [2][tiles + 1] their exclusive scans
+    uint8_t* out;           // [out_len]
+    int64_t out_len;
+    int64_t* out_off;       // [n_kept + 1]
+    int64_t* rows;          // [n_kept]
+    int64_t n_kept;
+};
+
+TRRE_HD void filter_part(const FilterArgs& a, int64_t tile, int64_t b) {
+    a.part[b] = b == 0 ? 0 : rec_lower_bound(RecEndKey{a.off}, a.nrec, b * tile - a.vbeg + 1);
+}
+TRRE_HD bool filter_kept(const FilterArgs& a, int64_t i) { return (a.loff[i + 1] > a.loff[i]) != (a.invert != 0u); }
+
+// tile b: the positions [t0, t1) of the input, the strings [i0, i1) that end in it, `per` of them to a thread
+template <class G>
+struct FilterTile {
+    int64_t s0, t0, t1, i0, i1, per;
+    TRRE_HD FilterTile(const FilterArgs& a, int64_t b) {
+        s0 = b * G::TILE;
+        t0 = s0 > a.vbeg ? s0 - a.vbeg : 0;
+        t1 = s0 + G::TILE - a.vbeg < a.n ? s0 + G::TILE - a.vbeg : a.n;
+        i0 = a.part[b]; i1 = a.part[b + 1];
+        per = (i1 - i0 + G::THREADS - 1) / G::THREADS;
+    }
+    TRRE_HD int64_t lo(int tid) const { return i0 + tid * per < i1 ? i0 + tid * per : i1; }
+    TRRE_HD int64_t hi(int tid) const { return lo(tid) + per < i1 ? lo(tid) + per : i1; }
+};
+// k_filter_count: the thread's kept strings and their bytes in the tile; thread 0 adds the string that covers the tile's end
+template <class G>
+TRRE_HD void filter_count_strings(const FilterArgs& a, const FilterTile<G>& t, int tid, uint64_t& rows, uint64_t& bytes) {
+    rows = bytes = 0;
+    const int64_t hi = t.hi(tid);
+    for (int64_t i = t.lo(tid); i < hi; ++i) {
+        if (!filter_kept(a, i)) continue;
+        ++rows;
+        const int64_t s = a.off[i] > t.t0 ? a.off[i] : t.t0, e = a.off[i + 1] < t.t1 ? a.off[i + 1] : t.t1;
+        if (e > s) bytes += (uint64_t)(e - s);
+    }
+    if (tid == 0 && t.i1 < a.nrec && filter_kept(a, t.i1)) {
+        const int64_t s = a.off[t.i1] > t.t0 ? a.off[t.i1] : t.t0;
+        if (t.t1 > s) bytes += (uint64_t)(t.t1 - s);
+    }
+}
+// k_filter_emit: the thread's source vectors of the tile (vector q = j * THREADS + tid: coalesced), asked for at once
+template <class G>
+TRRE_HD void filter_load_vecs(const FilterArgs& a, const FilterTile<G>& t, int tid, U128 (&w)[G::VECS]) {
+    for (int j = 0; j < G::VECS; ++j) {
+        const int64_t v = t.s0 + 16 * ((int64_t)j * G::THREADS + tid);
+        w[j].x = w[j].y = w[j].z = w[j].w = 0;                        // (behind the input's end: zeros)
+        if (v < a.vbeg + a.n) w[j] = rec_load16(a.in_v0 + v);
+    }
+}
+// ... into the LDS image: a vector of zeros, the tile's NVEC vectors, a vector of zeros (str_funnel16 reads from up to 15 bytes in
+// front of the tile and one vector behind)
+template <class G>
+TRRE_HD void filter_keep_vecs(int tid, const U128 (&w)[G::VECS], U128* lds) {
+    for (int j = 0; j < G::VECS; ++j) lds[1 + j * G::THREADS + tid] = w[j];
+    if (tid == 0) {
+        U128 z;
+        z.x = z.y = z.z = z.w = 0;
+        lds[0] = lds[G::NVEC + 1] = z;
+    }
+}
+TRRE_HD void filter_toggle(uint32_t* bits32, int64_t x, int64_t tile) {
+    if (x >= 0 && x < tile) TRRE_REC_LDS_XOR(bits32 + (x >> 5), 1u << (uint32_t)(x & 31));
+}
+// ... the toggles of the thread's kept strings (bits32: TILE / 32 words, zeroed before); returns the thread's kept strings
+template <class G>
+TRRE_HD uint64_t filter_mark(const FilterArgs& a, const FilterTile<G>& t, int tid, uint32_t* bits32) {
+    uint64_t rows = 0;
+    const int64_t hi = t.hi(tid);
+    for (int64_t i = t.lo(tid); i < hi; ++i) {
+        if (!filter_kept(a, i)) continue;
+        ++rows;
+        const int64_t s = a.off[i] > t.t0 ? a.off[i] : t.t0, e = a.off[i + 1];
+        if (e > s) {
+            filter_toggle(bits32, s + a.vbeg - t.s0, G::TILE);
+            filter_toggle(bits32, e + a.vbeg - t.s0, G::TILE);      // (an end on the tile's last byte toggles nothing: behind the image)
+        }
+    }
+    if (tid == 0 && t.i1 < a.nrec && filter_kept(a, t.i1)) {
+        const int64_t s = a.off[t.i1] > t.t0 ? a.off[t.i1] : t.t0;
+        if (t.t1 > s) filter_toggle(bits32, s + a.vbeg - t.s0, G::TILE);
+    }
+    return rows;
+}
+// toggles in the thread's rank segment, vectors [tid * VECS, tid * VECS + VECS): rec_seg_count.  Then, in place of the segment's
+// toggles, its kept bits (pre_t: toggles before the segment); returns the segment's kept bytes
+template <class G>
+TRRE_HD uint32_t filter_seg_kept(const FilterArgs& a, const FilterTile<G>& t, int tid, uint16_t* bits16, uint32_t pre_t) {
+    uint32_t d = pre_t & 1u, c = 0;
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        const int64_t v = t.s0 + 16 * (int64_t)q;
+        const uint32_t mk = bits16[q];
+        const uint32_t ok = v < a.vbeg + a.n ? rec_valid16(v, a.vbeg, a.vbeg + a.n) : 0u;
+        const uint32_t kp = (split_odd_below16(mk) ^ mk ^ (0u - d)) & ok;      // an odd number of toggles at or below the byte
+        bits16[q] = (uint16_t)kp;
+        c += rec_popc(kp);
+        d ^= rec_popc(mk) & 1u;
+    }
+    return c;
+}
+// kept bytes of the tile at byte indices < x (x in [0, TILE]; pv: str_fill_pv of the kept image)
+template <class G>
+TRRE_HD uint32_t filter_kept_below(const uint16_t* bits16, const uint32_t* pv, int64_t x) {
+    if (x >= G::TILE) return pv[G::NVEC];
+    if (x <= 0) return 0u;
+    return pv[x >> 4] + rec_popc(bits16[x >> 4] & ((1u << (uint32_t)(x & 15)) - 1u));
+}
+// ... behind the barrier that completes the kept image and pv: rows and out_off of the thread's kept strings (r0: kept strings of
+// the tile before the thread's)
+template <class G>
+TRRE_HD void filter_emit_rows(const FilterArgs& a, const FilterTile<G>& t, int64_t b, int tid, uint64_t r0, const uint16_t* bits16,
+                              const uint32_t* pv) {
+    if (b == 0 && tid == 0) a.out_off[0] = 0;
+    int64_t r = (int64_t)(a.base[b] + r0);
+    const int64_t k0 = (int64_t)a.base[a.tiles + 1 + b];
+    const int64_t hi = t.hi(tid);
+    for (int64_t i = t.lo(tid); i < hi; ++i) {
+        if (!filter_kept(a, i)) continue;
+        if (r < a.n_kept) {                                           // (never beyond: the totals were checked before this pass)
+            a.rows[r] = i;
+            a.out_off[r + 1] = k0 + (int64_t)filter_kept_below<G>(bits16, pv, a.off[i + 1] + a.vbeg - t.s0);
+        }
+        ++r;
+    }
+}
+// the bytes of a 32-bit word named by the 4-bit mask m4, as 0xff each
+TRRE_HD uint32_t filter_bytes4(uint32_t m4) { return ((m4 * 0x00204081u) & 0x01010101u) * 0xffu; }
+TRRE_HD uint32_t filter_get_byte(const U128& r, int k) {
+    const uint32_t w = k < 4 ? r.x : k < 8 ? r.y : k < 12 ? r.z : r.w;
+    return (w >> (8u * (uint32_t)(k & 3))) & 0xffu;
+}
+// ... the tile's E kept bytes to out + kbase[b].  Destination vector g of the address holds kept bytes [e0, e1), which are one
+// or more RUNS of consecutive source bytes.  The first byte of a run is found by its rank (rec_select), its length is the kept
+// bits in a row from there, and the run's bytes are str_funnel16 of the image from k bytes in front of it, k the run's place in
+// the vector — so 16 source bytes in one run are one funnel and one store, and a vector of r runs takes r of each, merged under
+// byte masks.  (lds: filter_keep_vecs' image, the tile's byte x at 16 + x)
+template <class G>
+TRRE_HD void filter_emit_vecs(const FilterArgs& a, int64_t b, int tid, const U128* lds, const uint16_t* bits16, const uint32_t* pre,
+                              const uint32_t* pv) {
+    const int64_t d0 = (int64_t)a.base[a.tiles + 1 + b], E = pv[G::NVEC];
+    const int A = (int)((reinterpret_cast<uintptr_t>(a.out) + (uintptr_t)d0) & 15u);
+    const int ng = E ? (int)((E + A + 15) >> 4) : 0;
+    for (int g = tid; g < ng; g += G::THREADS) {
+        const int64_t e0 = g ? 16 * (int64_t)g - A : 0;
+        const int64_t e1 = 16 * (int64_t)g - A + 16 < E ? 16 * (int64_t)g - A + 16 : E;
+        if (d0 + e1 > a.out_len) continue;                            // (never: the totals were checked before this pass)
+        const int cnt = (int)(e1 - e0);
+        int64_t x = rec_select<G>(bits16, pre, (uint32_t)e0 + 1u);
+        U128 r;
+        r.x = r.y = r.z = r.w = 0;
+        for (int k = 0;;) {
+            const int q = (int)(x >> 4);
+            const uint32_t ahead = ((uint32_t)bits16[q] | (q + 1 < G::NVEC ? (uint32_t)bits16[q + 1] << 16 : 0u)) >> (uint32_t)(x & 15);
+            int L = __builtin_ctz(~ahead | 0x10000u);                 // kept bytes in a row from x: 1 .. 16
+            if (L > cnt - k) L = cnt - k;
+            const U128 f = str_funnel16(lds, x + 16 - k);
+            const uint32_t m = ((1u << (uint32_t)L) - 1u) << (uint32_t)k;
+            r.x |= f.x & filter_bytes4(m & 15u); r.y |= f.y & filter_bytes4((m >> 4) & 15u);
+            r.z |= f.z & filter_bytes4((m >> 8) & 15u); r.w |= f.w & filter_bytes4((m >> 12) & 15u);
+            k += L;
+            if (k >= cnt) break;
+            x = rec_select<G>(bits16, pre, (uint32_t)(e0 + k) + 1u);
+        }
+        uint8_t* d = a.out + d0 + e0;
+        if (cnt == 16) {
+            rec_store16(d, r);
+        } else {
+            for (int k = 0; k < cnt; ++k) d[k] = (uint8_t)filter_get_byte(r, k);
+        }
+    }
+}
+
 }  // namespace trre

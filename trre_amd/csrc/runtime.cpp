@@ -172,6 +172,7 @@ struct ScanCtx {
     DevBuf<uint64_t> d_match;         // trre_match_device_strings: accepted strings per group of 256, then their exclusive scan [groups + 1] (groups)
     DevBuf<int64_t> d_find_off;       // trre_find_device_strings: the list offsets while they are ranks and located positions [nrec + 1] (entries)
     DevBuf<uint8_t> d_find_marks;     // ... the marks scan unframed: a byte per match (bytes)
+    DevBuf<int64_t> d_filter_lists;   // trre_filter_device_strings: the span call's list offsets, which give the verdicts [nrec + 1] (entries)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
     DevBuf<uint32_t> d_cevents, d_chdr;
@@ -659,7 +660,7 @@ constexpr uint64_t kGuardBudget = 1ull << 23;              // search steps per l
 constexpr uint64_t kGuardCallBudget = 1ull << 35;
 constexpr const char* kStackMsg = "error: stack max capacity reached";
 constexpr const char* kFindOnlyMsg = "error: a program compiled with TRRE_MODE_FIND runs through trre_find_device_strings only";
-constexpr const char* kSpansOnlyMsg = "error: a program compiled with TRRE_MODE_SPANS runs through trre_span_device_strings and trre_split_device_strings only";
+constexpr const char* kSpansOnlyMsg = "error: a program compiled with TRRE_MODE_SPANS runs through trre_span_device_strings, trre_split_device_strings and trre_filter_device_strings only";
 constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
 // a program that one call alone runs: that call's name for every other call's refusal (null: any scan call may run it)
 const char* own_call_only(const trre_prog& p) {
@@ -2940,6 +2941,87 @@ int trre_split_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     std::lock_guard<std::mutex> lock(st->mu);
     if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
     return split_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_piece_off, piece_cap, d_list_off, n_pieces, out_len, static_cast<hipStream_t>(stream));
+}
+
+// the strings with a match (without one: TRRE_FILTER_INVERT), whole, and their rows: steps 1 - 5 are the span call's
+static int filter_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint32_t flags, uint8_t* d_out,
+                     size_t cap, int64_t* d_out_off, int64_t* d_rows, size_t row_cap, size_t* n_kept, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    SpanMarks mk;
+    int rc = span_marks(p, st, d_in, n, d_off, nrec, false, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 6. the span call's list offsets, and nothing else of it, into the library's own array: the verdicts
+    HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
+    SpanArgs& pa = mk.pa;
+    pa.start = pa.end = nullptr; pa.list_off = cx->d_filter_lists; pa.n_match = 0; pa.lists_only = 1u;
+    launch_span_emit(pa, s);
+    // 7. over tiles of the INPUT: the first string of every tile, the kept strings and bytes per tile and before it (behind the
+    //    status word: part [tiles + 1], cnt [2][tiles], base [2][tiles + 1]); the two totals in one read-back
+    const int64_t T = str_tile_bytes();
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    const int64_t tiles = std::max<int64_t>((a0 + (int64_t)n + T - 1) / T, 1);
+    RecCarve c;                                             // (room as for 2 tiles + 1: 6 tiles + 6 words)
+    rc = rec_carve(cx, 2 * tiles + 1, &c);
+    if (rc) return rc;
+    FilterArgs a{};
+    a.in_v0 = d_in - a0; a.vbeg = a0; a.n = (int64_t)n; a.off = d_off; a.loff = cx->d_filter_lists; a.nrec = (int64_t)nrec;
+    a.invert = (flags & TRRE_FILTER_INVERT) ? 1u : 0u; a.tiles = tiles;
+    a.part = c.part; a.cnt = reinterpret_cast<uint64_t*>(c.part) + tiles + 1; a.base = a.cnt + 2 * tiles;
+    launch_filter_count(a, s);
+    uint64_t tot[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        uint64_t* base = const_cast<uint64_t*>(a.base) + k * (tiles + 1);
+        launch_chunk_scan(a.cnt + k * tiles, base, tiles, s);
+        HIP_TRY(hipMemcpyAsync(&tot[k], base + tiles, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (tot[0] > nrec || tot[1] > n) return fail(TRRE_E_DEVICE, "error: the kept strings do not add up (internal)");
+    const size_t kept = (size_t)tot[0], bytes = (size_t)tot[1];
+    if (n_kept) *n_kept = kept;
+    if (out_len) *out_len = bytes;
+    if (bytes > cap || kept > row_cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    // 8. the kept strings' bytes, where each starts and which row it was
+    if (kept == 0) {
+        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+    } else {
+        a.out = d_out; a.out_len = (int64_t)bytes; a.out_off = d_out_off; a.rows = d_rows; a.n_kept = (int64_t)kept;
+        launch_filter_emit(a, s);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return TRRE_OK;
+}
+
+int trre_filter_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint32_t flags, uint8_t* d_out,
+                               size_t cap, int64_t* d_out_off, int64_t* d_rows, size_t row_cap, size_t* n_kept, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_kept) *n_kept = 0;
+    if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (row_cap && (!d_out_off || !d_rows))) return fail(TRRE_E_ARG, "error: null argument");
+    if (flags & ~TRRE_FILTER_INVERT) return fail(TRRE_E_ARG, "error: unknown flag (TRRE_FILTER_INVERT is the only one)");
+    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: filtered strings take a program compiled with TRRE_MODE_SPANS");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || row_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    const size_t ob = (nrec + 1) * 8, pb = d_out_off ? (row_cap + 1) * 8 : 0, rb = d_rows ? row_cap * 8 : 0, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the kept strings are not made in place)");
+    if (ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cb) || ranges_overlap(d_out_off, pb, d_in, n) ||
+        ranges_overlap(d_out_off, pb, d_out, cb) || ranges_overlap(d_out_off, pb, d_off, ob) || ranges_overlap(d_rows, rb, d_in, n) ||
+        ranges_overlap(d_rows, rb, d_out, cb) || ranges_overlap(d_rows, rb, d_off, ob) || ranges_overlap(d_rows, rb, d_out_off, pb))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    DeviceState* st;
+    const int rc = current_state(p, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+    return filter_on(p, st, d_in, n, d_off, nrec, flags, d_out, cap, d_out_off, d_rows, row_cap, n_kept, out_len, static_cast<hipStream_t>(stream));
 }
 
 namespace {

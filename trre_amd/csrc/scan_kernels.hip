@@ -1881,6 +1881,79 @@ __global__ __launch_bounds__(SG::THREADS) void k_split_emit(SplitArgs a) {
     split_emit_pieces<SG>(a, b, tid, bits, kept, pv_ab, pv_nl, pv_k);
 }
 
+// ---- filtered strings (records_block.hpp; runtime.cpp: trre_filter_device_strings) -----------------------------------------
+using FG = StrGeoDev;
+static_assert(FG::THREADS == RG::THREADS && FG::THREADS % kWave == 0, "rec_block_scan");
+
+__global__ __launch_bounds__(256) void k_filter_part(FilterArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b <= a.tiles) filter_part(a, FG::TILE, b);
+}
+
+// The kept strings that end in the tile and the tile's kept bytes, from the offsets and the list offsets alone.
+__global__ __launch_bounds__(FG::THREADS) void k_filter_count(FilterArgs a) {
+    __shared__ uint64_t wsum[2][FG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const FilterTile<FG> t(a, b);
+    uint64_t rows, bytes;
+    filter_count_strings<FG>(a, t, tid, rows, bytes);
+    rows = wave_sum(rows);
+    bytes = wave_sum(bytes);
+    if ((tid & (kWave - 1)) == 0) { wsum[0][tid / kWave] = rows; wsum[1][tid / kWave] = bytes; }
+    __syncthreads();
+    if (tid < 2) {
+        uint64_t s = 0;
+        for (int k = 0; k < FG::THREADS / kWave; ++k) s += wsum[tid][k];
+        a.cnt[(int64_t)tid * a.tiles + b] = s;
+    }
+}
+
+// The kept strings' bytes, their rows and where each starts.  Barriers: behind the zeroing of the toggle image, before the XORs;
+// behind the XORs and the byte image, which every later step reads across threads; the scans' own between pre and its readers
+// (a thread turns its own segment's toggles into kept bits in place: nobody else reads them in between); one more behind pv,
+// after which the image, pre and pv are only read.  A thread's rank among the tile's kept strings is the scan of the threads'
+// counts: 23 bits at a time when 2^30 strings or more end in one tile, so that no partial sum leaves 32 bits.
+__global__ __launch_bounds__(FG::THREADS) void k_filter_emit(FilterArgs a) {
+    __shared__ U128 lds[FG::NVEC + 2];
+    __shared__ uint32_t bits32[FG::NVEC / 2];
+    __shared__ uint32_t pv[FG::NVEC + 1];
+    __shared__ uint32_t pre[FG::THREADS];
+    __shared__ uint32_t wtot[FG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const FilterTile<FG> t(a, b);
+    U128 w[FG::VECS];
+    filter_load_vecs<FG>(a, t, tid, w);              // the tile's bytes are on their way while the strings are looked up
+    for (int k = tid; k < FG::NVEC / 2; k += FG::THREADS) bits32[k] = 0;
+    __syncthreads();
+    const uint64_t mine = filter_mark<FG>(a, t, tid, bits32);
+    filter_keep_vecs<FG>(tid, w, lds);
+    __syncthreads();
+    rec_block_scan((uint32_t)(mine & 0x7fffffu), pre, wtot);
+    uint64_t r0 = pre[tid];
+    if (t.i1 - t.i0 >= ((int64_t)1 << 30)) {         // (the same for every thread of the workgroup)
+        rec_block_scan((uint32_t)(mine >> 23), pre, wtot);
+        r0 += (uint64_t)pre[tid] << 23;
+    }
+    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
+    rec_block_scan(rec_seg_count<FG>(bits16, tid), pre, wtot);
+    rec_block_scan(filter_seg_kept<FG>(a, t, tid, bits16, pre[tid]), pre, wtot);
+    str_fill_pv<FG>(bits16, pre[tid], tid, pv);
+    __syncthreads();
+    filter_emit_rows<FG>(a, t, b, tid, r0, bits16, pv);
+    filter_emit_vecs<FG>(a, b, tid, lds, bits16, pre, pv);
+}
+
+void launch_filter_count(const FilterArgs& a, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_filter_part, dim3((unsigned)((a.tiles + 1 + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_filter_count, dim3((unsigned)a.tiles), dim3(FG::THREADS), 0, s, a);
+}
+void launch_filter_emit(const FilterArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_filter_emit, dim3((unsigned)a.tiles), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+
 void launch_split_count(const SplitArgs& a, void* stream) {
     hipLaunchKernelGGL(k_split_count, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
 }
