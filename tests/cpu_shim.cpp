@@ -247,7 +247,7 @@ void run_direct_gen_exact(ScanArgs a, int64_t lane_bytes, uint32_t& status, uint
         }
         if (!bad) break;
         ++rounds;
-        if (rounds > n_lanes + 8) { status |= 1u << 29; return; }      // must not happen
+        if (rounds > n_lanes + 8) { status |= 1u << 29; return; }      // (a round settles at least the leftmost flagged lane: more rounds than lanes must not happen)
         a.exact = 3;
         const std::vector<uint32_t> exits_before = exits;               // (what the threads of one launch read of the lanes before them: maybe stale)
         for (int64_t lane = n_lanes - 1; lane >= 1; --lane) {
@@ -649,7 +649,7 @@ extern "C" {
 // family: 1 bytemap, 2 tile LP, 3 tile general (4 / 5, the LDS-tile walkers of the stream tables, went in round 6).
 // 20 / 21 stream LP by the emit pass alone (16-byte / 8-byte entries),
 // 8 positional-window stream LP, 9 direct stream general on the 8-byte entries (7 prefers the 16-byte ones), 6 direct stream LP, 7 direct stream general (geo: 0 -> 2048-byte lanes, 1 -> 48-byte lanes).
-// geo: 0 production, 1 tiny.
+// geo: 0 production, 1 tiny; 2 (the exact sub-ranges, families 32 / 33 and 17 / 18): lanes of 128 bytes in workgroups of 256.
 // in_mis/out_mis: address misalignment (0..15) to give the staged buffers.
 // want_scratch: pass a mask scratch to the NFT long-line path.
 int shim_scan(const uint8_t* blob, int engine, int mask_bytes, int family, int geo, const uint8_t* in, size_t n,
@@ -704,7 +704,8 @@ int shim_scan(const uint8_t* blob, int engine, int mask_bytes, int family, int g
     else if (family == 32 || family == 33) {          // ... with exact sub-ranges (33: a look-back of 4 bytes: wrong guesses, repair rounds)
         if (reinterpret_cast<const StreamBlobHeader*>(blob)->g16_bytes == 0) return -5;
         int rounds = 0;
-        run_direct_gen_exact<>(a, geo == 0 ? 2048 : 64, status, total, family == 33 ? 4u : (uint32_t)kSpecLook, geo == 0 ? 256 : 3, rounds);
+        // (geo 2: lanes of 128 bytes in workgroups of 256, what TRRE_LANE_BYTES=128 runs on the device)
+        run_direct_gen_exact<>(a, geo == 0 ? 2048 : geo == 2 ? 128 : 64, status, total, family == 33 ? 4u : (uint32_t)kSpecLook, geo == 1 ? 3 : 256, rounds);
         g_last_rounds = rounds;
     }
     else if (family == 37 || family == 38) {          // a memoryless program in one pass (map_block.hpp); 38: tiles of 3 threads, windows of 48 bytes
@@ -824,8 +825,8 @@ int shim_scan_guided(const uint8_t* rblob, const uint8_t* gblob, int family, int
         // general guided family with exact sub-ranges (18: a look-back of 4 bytes: wrong guesses, repair rounds)
         if (!has_g16) return -5;
         int rounds = 0;
-        if (packed) run_direct_gen_exact<2>(a, lane_bytes, status, total, family == 18 ? 4u : (uint32_t)kSpecLook, geo == 0 ? 256 : 3, rounds);
-        else run_direct_gen_exact<1>(a, lane_bytes, status, total, family == 18 ? 4u : (uint32_t)kSpecLook, geo == 0 ? 256 : 3, rounds);
+        if (packed) run_direct_gen_exact<2>(a, lane_bytes, status, total, family == 18 ? 4u : (uint32_t)kSpecLook, geo == 1 ? 3 : 256, rounds);
+        else run_direct_gen_exact<1>(a, lane_bytes, status, total, family == 18 ? 4u : (uint32_t)kSpecLook, geo == 1 ? 3 : 256, rounds);
         g_last_rounds = rounds + rev_rounds;
     }
     else if (family == 40 || family == 41) {

@@ -1487,7 +1487,12 @@ int exact_repair(const Finishing& f, uint32_t* status) {
     const int64_t n_lanes = (xa.vend + pl.lane_bytes - 1) / pl.lane_bytes;
     for (int64_t round = 0; misses; ++round) {
         if (switches().trace) fprintf(stderr, "trre: exact sub-ranges: round %lld, %u lane(s) to repair\n", (long long)round, misses);
-        if (round > pl.n_chunks + 64)           // (every round settles at least the first flagged lane's workgroup: cannot happen)
+        // A round settles a workgroup where ONE lane of it is flagged (the parity of `aa:x` in a run of `a`: the lanes behind the flagged one agree
+        // with each other and the walk passes through them).  Where flagged lanes are neighbours — `aaa:xy` in such a run: two lanes in three —
+        // a flagged lane ends the walk of the one before it and starts from an exit that is being rewritten: a round settles ONE lane, and a run
+        // over more than n_chunks + 64 lanes ends here, scanned again the old way (tests/test_gpu_exact_repair.py: long_run_aaa_dft).  To do:
+        // let a flagged lane walk on through flagged lanes — it knows their true entry.
+        if (round > pl.n_chunks + 64)
             return rerun(f, was.family, &ScanCtx::exact_off, false);
         HIP_TRY(hipMemsetAsync(cx->d_status + 3, 0, 4, was.stream));
         xa.exact = 3;
