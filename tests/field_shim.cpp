@@ -16,53 +16,11 @@
 #include <cstring>
 #include <vector>
 
-#include "../trre_amd/csrc/records_block.hpp"
+#include "column_shim.hpp"
 
 using namespace trre;
 
 namespace {
-
-constexpr int64_t kUnstored = (int64_t)0xEEEEEEEEEEEEEEEEull;
-constexpr uint8_t kUnstoredByte = 0xEE;      // (no source byte of a test is this one)
-constexpr int kPad = 8;
-
-template <class P>
-P* shifted(P* p, int64_t elements) {
-    return reinterpret_cast<P*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)elements * sizeof(P));
-}
-
-// an array of n elements with kPad sentinel elements on either side, element 0 at an address that is `mis` mod 16
-template <class E>
-struct Padded {
-    std::vector<E> w;
-    E fill;
-    size_t at;
-    Padded(int64_t n, E f, int mis = 0) : w((size_t)n + 2 * kPad + 32, f), fill(f), at(kPad) {
-        if (sizeof(E) == 1)
-            while ((reinterpret_cast<uintptr_t>(w.data() + at) & 15u) != (uintptr_t)mis) ++at;
-        w.resize(at + (size_t)n + kPad);         // (shrinks: the storage stays where it is)
-    }
-    E* data() { return w.data() + at; }
-    bool pads_intact() const {
-        for (size_t k = 0; k < at; ++k)
-            if (w[k] != fill) return false;
-        for (int k = 0; k < kPad; ++k)
-            if (w[w.size() - 1 - (size_t)k] != fill) return false;
-        return true;
-    }
-};
-
-// elements that changed; *twice when one that had been stored before changed again
-template <class E>
-int64_t changed(const std::vector<E>& now, const std::vector<E>& was, E fill, bool* twice) {
-    int64_t c = 0;
-    for (size_t k = 0; k < now.size(); ++k)
-        if (now[k] != was[k]) {
-            if (was[k] != fill) *twice = true;
-            ++c;
-        }
-    return c;
-}
 
 struct Column {
     const uint8_t* in; int64_t n;            // the strings' bytes
@@ -228,11 +186,6 @@ int run(const Column& c, const Result& r) {
     std::memcpy(r.out_off, wf.data(), (size_t)(nrec + 1) * 8);
     return wo.pads_intact() && wf.pads_intact() && wv.pads_intact() && wlo.pads_intact() && whi.pads_intact() ? 0 : 8;
 }
-
-using Geo0 = RecGeo<64, 1>;    // 1 KiB tiles, one wave
-using Geo1 = RecGeo<128, 1>;   // 2 KiB, two waves
-using Geo2 = RecGeo<64, 2>;    // 2 KiB, one wave, two vectors per thread
-using Geo3 = StrGeoDev;        // the device's
 
 }  // namespace
 

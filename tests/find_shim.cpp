@@ -13,7 +13,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../trre_amd/csrc/records_block.hpp"
+#include "column_shim.hpp"
 
 using namespace trre;
 
@@ -35,11 +35,6 @@ struct Aligned {
         return true;
     }
 };
-
-template <class P>
-P* shifted(P* p, int64_t elements) {
-    return reinterpret_cast<P*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)elements * sizeof(P));
-}
 
 template <class G>
 struct Lds {
@@ -113,11 +108,6 @@ int unframe(const uint8_t* framed, int64_t m, int64_t found, int64_t dst_mis, in
         if (words[k] != (int64_t)0xEEEEEEEEEEEEEEEEull || words[(size_t)found + 9 + k] != (int64_t)0xEEEEEEEEEEEEEEEEull) return 8;
     return dst.untouched_outside(dst_mis, dst_mis + m - found) ? 0 : 2;
 }
-
-using Geo0 = RecGeo<64, 1>;    // 1 KiB tiles, one wave
-using Geo1 = RecGeo<128, 1>;   // 2 KiB, two waves
-using Geo2 = RecGeo<64, 2>;    // 2 KiB, one wave, two vectors per thread
-using Geo3 = StrGeoDev;        // the device's
 
 }  // namespace
 

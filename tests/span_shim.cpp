@@ -13,31 +13,11 @@
 #include <cstring>
 #include <vector>
 
-#include "../trre_amd/csrc/records_block.hpp"
+#include "column_shim.hpp"
 
 using namespace trre;
 
 namespace {
-
-constexpr int64_t kUnstored = (int64_t)0xEEEEEEEEEEEEEEEEull;
-constexpr int kPad = 8;
-
-template <class P>
-P* shifted(P* p, int64_t elements) {
-    return reinterpret_cast<P*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)elements * sizeof(P));
-}
-
-// an array of n words with kPad sentinel words on either side
-struct Words {
-    std::vector<int64_t> w;
-    explicit Words(int64_t n) : w((size_t)n + 2 * kPad, kUnstored) {}
-    int64_t* data() { return w.data() + kPad; }
-    bool pads_intact() const {
-        for (int k = 0; k < kPad; ++k)
-            if (w[(size_t)k] != kUnstored || w[w.size() - 1 - (size_t)k] != kUnstored) return false;
-        return true;
-    }
-};
 
 // k_span_count, k_chunk_scan (three times), k_span_emit
 template <class G>
@@ -50,7 +30,7 @@ int run(const uint8_t* framed, int64_t m, int64_t found, int64_t lines, int list
     if (m) std::memcpy(v0, framed, (size_t)m);
     const int64_t b0 = pos0 / G::TILE, tiles = (m + G::TILE - 1) / G::TILE;
     std::vector<uint64_t> cnt((size_t)(3 * tiles) + 1, 0), base((size_t)(3 * (tiles + 1)), 0);
-    Words ws(found), we(found), wl(lines + 1);
+    Padded<int64_t> ws(found, kUnstored), we(found, kUnstored), wl(lines + 1, kUnstored);
     SpanArgs a{};
     a.src = shifted(v0, pos0); a.total = pos0 + m; a.tiles = tiles;
     a.cnt = shifted(cnt.data(), b0); a.base = shifted(static_cast<const uint64_t*>(base.data()), b0);
@@ -98,24 +78,14 @@ int run(const uint8_t* framed, int64_t m, int64_t found, int64_t lines, int list
         // (barrier) the words: wave by wave, the lanes of a wave in turn; a word may be stored once
         const std::vector<int64_t> bs(ws.w), be(we.w), bl(wl.w);
         for (int tid = 0; tid < G::THREADS; ++tid) span_emit_pieces<G>(a, b, tid, bits.data(), pv_ab.data(), pv_nl.data());
-        const std::vector<int64_t>* now[3] = {&ws.w, &we.w, &wl.w};
-        const std::vector<int64_t>* was[3] = {&bs, &be, &bl};
-        for (int x = 0; x < 3; ++x)
-            for (size_t k = 0; k < now[x]->size(); ++k)
-                if ((*now[x])[k] != (*was[x])[k]) {
-                    if ((*was[x])[k] != kUnstored) return 7;                            // a word stored by two tiles
-                    *stores += 1;
-                }
+        bool twice = false;
+        *stores += changed(ws.w, bs, kUnstored, &twice) + changed(we.w, be, kUnstored, &twice) + changed(wl.w, bl, kUnstored, &twice);
+        if (twice) return 7;                                                            // a word stored by two tiles
     }
     if (found) { std::memcpy(start, ws.data(), (size_t)found * 8); std::memcpy(end, we.data(), (size_t)found * 8); }
     std::memcpy(list_off, wl.data(), (size_t)(lines + 1) * 8);
     return ws.pads_intact() && we.pads_intact() && wl.pads_intact() ? 0 : 8;
 }
-
-using Geo0 = RecGeo<64, 1>;    // 1 KiB tiles, one wave
-using Geo1 = RecGeo<128, 1>;   // 2 KiB, two waves
-using Geo2 = RecGeo<64, 2>;    // 2 KiB, one wave, two vectors per thread
-using Geo3 = StrGeoDev;        // the device's
 
 }  // namespace
 

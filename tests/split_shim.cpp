@@ -13,46 +13,11 @@
 #include <cstring>
 #include <vector>
 
-#include "../trre_amd/csrc/records_block.hpp"
+#include "column_shim.hpp"
 
 using namespace trre;
 
 namespace {
-
-constexpr int64_t kUnstored = (int64_t)0xEEEEEEEEEEEEEEEEull;
-constexpr uint8_t kUnstoredByte = 0xEE;      // (no source byte of a test is this one)
-constexpr int kPad = 8;
-
-template <class P>
-P* shifted(P* p, int64_t elements) {
-    return reinterpret_cast<P*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)elements * sizeof(P));
-}
-
-// an array of n elements with kPad sentinel elements on either side
-template <class E>
-struct Padded {
-    std::vector<E> w;
-    E fill;
-    Padded(int64_t n, E f) : w((size_t)n + 2 * kPad, f), fill(f) {}
-    E* data() { return w.data() + kPad; }
-    bool pads_intact() const {
-        for (int k = 0; k < kPad; ++k)
-            if (w[(size_t)k] != fill || w[w.size() - 1 - (size_t)k] != fill) return false;
-        return true;
-    }
-};
-
-// elements that changed; *twice when one that had been stored before changed again
-template <class E>
-int64_t changed(const std::vector<E>& now, const std::vector<E>& was, E fill, bool* twice) {
-    int64_t c = 0;
-    for (size_t k = 0; k < now.size(); ++k)
-        if (now[k] != was[k]) {
-            if (was[k] != fill) *twice = true;
-            ++c;
-        }
-    return c;
-}
 
 // k_span_count, k_chunk_scan (three times), k_split_count, k_chunk_scan, k_split_emit
 template <class G>
@@ -163,11 +128,6 @@ int run(const uint8_t* framed, int64_t m, const uint8_t* in, int64_t n, int64_t 
     std::memcpy(list_off, wl.data(), (size_t)(lines + 1) * 8);
     return wo.pads_intact() && wp.pads_intact() && wl.pads_intact() ? 0 : 8;
 }
-
-using Geo0 = RecGeo<64, 1>;    // 1 KiB tiles, one wave
-using Geo1 = RecGeo<128, 1>;   // 2 KiB, two waves
-using Geo2 = RecGeo<64, 2>;    // 2 KiB, one wave, two vectors per thread
-using Geo3 = StrGeoDev;        // the device's
 
 }  // namespace
 

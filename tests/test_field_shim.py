@@ -6,17 +6,12 @@ before the shim runs.  Checked: lo and hi of every string, each stored exactly o
 bitmap's words and tail bits; the fields' bytes in input order; out_off, entry 0 by tile 0 alone and every other byte and word
 once; nothing behind out_len, nrec + 1 and the bitmap's last word."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "field_shim.cpp")
-HDR = os.path.join(os.path.dirname(HERE), "trre_amd", "csrc", "records_block.hpp")
-SO = os.path.join(HERE, "_shim", "libfield_shim.so")
-DEPS = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
+import column_shim_lib
+
 GEOS = (0, 1, 2, 3)
 UNSTORED = np.int64(-0x1111111111111112)          # 0xEEEE... as a signed word
 KS = (0, 1, 2, -1, -2, 5, -(1 << 63))
@@ -27,10 +22,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not (os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in DEPS)):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", SO], check=True)
-        L = ctypes.CDLL(SO)
+        L = column_shim_lib.load("field")
         vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
         L.shim_field_tile.argtypes = [i32]
         L.shim_field_tile.restype = i64
@@ -320,10 +312,5 @@ def test_bases_and_ranks_beyond_32_bits():
 def test_stand_alone_program_under_sanitizers():
     """field_shim.cpp with its own main, built with -fsanitize=address,undefined, over generated lengths, columns, k from both
     ends and out of range, misalignments and the shift beyond 2^32: a process of its own, on the CPU"""
-    exe = os.path.join(HERE, "_shim", "field_shim_san")
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-DFIELD_SHIM_MAIN", SRC, "-o", exe], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = column_shim_lib.sanitized("field")
     assert r.returncode == 0 and b"shapes ok" in r.stdout and not r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-2000:])

@@ -4,17 +4,12 @@ against numpy.  String i is kept exactly when (list_off[i + 1] > list_off[i]) !=
 order, kept string r starts at out_off[r] and was row rows[r]; out_off[0] is stored by tile 0 alone, every other byte and word
 once, and nothing behind out_len, n_kept + 1 and n_kept."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "filter_shim.cpp")
-HDR = os.path.join(os.path.dirname(HERE), "trre_amd", "csrc", "records_block.hpp")
-SO = os.path.join(HERE, "_shim", "libfilter_shim.so")
-DEPS = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
+import column_shim_lib
+
 GEOS = (0, 1, 2, 3)
 UNSTORED = np.int64(-0x1111111111111112)          # 0xEEEE... as a signed word
 FAR = dict(rr0=(1 << 33) + 7, rk0=(1 << 34) + 11)
@@ -25,10 +20,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not (os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in DEPS)):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", SO], check=True)
-        L = ctypes.CDLL(SO)
+        L = column_shim_lib.load("filter")
         vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
         L.shim_filter_tile.argtypes = [i32]
         L.shim_filter_tile.restype = i64
@@ -225,10 +217,5 @@ def test_bases_and_ranks_beyond_32_bits():
 def test_stand_alone_program_under_sanitizers():
     """filter_shim.cpp with its own main, built with -fsanitize=address,undefined, over the same lengths, columns, misalignments,
     both senses and the shift beyond 2^32: a process of its own, on the CPU"""
-    exe = os.path.join(HERE, "_shim", "filter_shim_san")
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-DFILTER_SHIM_MAIN", SRC, "-o", exe], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = column_shim_lib.sanitized("filter")
     assert r.returncode == 0 and b"shapes ok" in r.stdout and not r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-2000:])

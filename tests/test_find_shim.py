@@ -3,17 +3,12 @@ behind k_match_count and k_chunk_scan) run on the host by tests/find_shim.cpp â€
 framed newline number j at framed position q closes match j, match_off[j + 1] = q - j, match_off[0] = 0 is stored by tile 0
 alone, every other word once, and the output is the framed text without its newlines."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "find_shim.cpp")
-HDR = os.path.join(os.path.dirname(HERE), "trre_amd", "csrc", "records_block.hpp")
-SO = os.path.join(HERE, "_shim", "libfind_shim.so")
-DEPS = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
+import column_shim_lib
+
 GEOS = (0, 1, 2, 3)
 UNSTORED = -0x1111111111111112          # 0xEE..EE as int64: a word nobody stored
 
@@ -23,10 +18,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not (os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in DEPS)):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", SO], check=True)
-        L = ctypes.CDLL(SO)
+        L = column_shim_lib.load("find")
         vp, i64 = ctypes.c_void_p, ctypes.c_int64
         L.shim_find_tile.argtypes = [ctypes.c_int]
         L.shim_find_tile.restype = i64
@@ -127,10 +119,5 @@ def test_tile_base_beyond_32_bits():
 def test_stand_alone_program_under_sanitizers():
     """find_shim.cpp with its own main, built with -fsanitize=address,undefined, over the same lengths, patterns, misalignments
     and the shift beyond 2^32: a process of its own, on the CPU"""
-    exe = os.path.join(HERE, "_shim", "find_shim_san")
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-DFIND_SHIM_MAIN", SRC, "-o", exe], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = column_shim_lib.sanitized("find")
     assert r.returncode == 0 and b"shapes ok" in r.stdout and not r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-2000:])

@@ -5,18 +5,13 @@ base: ranks beyond 2^32), the final offsets and the compaction, composed with th
 (tests/records_shim.cpp) around a stand-in scan that prints accepted lines only.  Symbols are given as arrays in the three
 layouts the backward pass has (two per byte, one per byte, 16 bits each)."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 
+import column_shim_lib
 from test_records_shim import lib as rec_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "match_shim.cpp")
-HDR = os.path.join(os.path.dirname(HERE), "trre_amd", "csrc", "records_block.hpp")
-SO = os.path.join(HERE, "_shim", "libmatch_shim.so")
 GEOS = (0, 1, 2, 3)
 N_REV = {4: 16, 8: 200, 16: 700}
 
@@ -26,11 +21,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        deps = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
-        if not (os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in deps)):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", SO], check=True)
-        L = ctypes.CDLL(SO)
+        L = column_shim_lib.load("match")
         vp, i64, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64
         L.shim_match_group.restype = i64
         L.shim_match_tile.argtypes = [ctypes.c_int]
@@ -254,11 +245,5 @@ def test_device_geometry():
 def test_stand_alone_program_under_sanitizers():
     """match_shim.cpp with its own main, built with -fsanitize=address,undefined, over nrec around the words and groups, seven
     verdict patterns, the three symbol layouts and the destination misalignments: a process of its own, on the CPU"""
-    exe = os.path.join(HERE, "_shim", "match_shim_san")
-    deps = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-DMATCH_SHIM_MAIN", SRC, "-o", exe], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = column_shim_lib.sanitized("match")
     assert r.returncode == 0 and b"shapes ok" in r.stdout and not r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-2000:])

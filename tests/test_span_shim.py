@@ -4,17 +4,12 @@ b, l the A (0x01), B (0x02) and newlines before framed position q: A number j at
 gives end[j] by the same expression, newline number i gives list_off[i + 1] = a; list_off[0] = 0 is stored by tile 0 alone,
 every other word once, by the lane that owns its marker."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "span_shim.cpp")
-HDR = os.path.join(os.path.dirname(HERE), "trre_amd", "csrc", "records_block.hpp")
-SO = os.path.join(HERE, "_shim", "libspan_shim.so")
-DEPS = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
+import column_shim_lib
+
 GEOS = (0, 1, 2, 3)
 UNSTORED = -0x1111111111111112          # 0xEE..EE as int64: a word nobody stored
 A, B, NL, DOT = 1, 2, 10, ord(".")
@@ -25,10 +20,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not (os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in DEPS)):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", SO], check=True)
-        L = ctypes.CDLL(SO)
+        L = column_shim_lib.load("span")
         vp, i64 = ctypes.c_void_p, ctypes.c_int64
         L.shim_span_tile.argtypes = [ctypes.c_int]
         L.shim_span_tile.restype = i64
@@ -184,10 +176,5 @@ def test_bases_and_ranks_beyond_32_bits():
 def test_stand_alone_program_under_sanitizers():
     """span_shim.cpp with its own main, built with -fsanitize=address,undefined, over the same lengths, patterns, the
     list-offsets-only flag and the shift beyond 2^32: a process of its own, on the CPU"""
-    exe = os.path.join(HERE, "_shim", "span_shim_san")
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-DSPAN_SHIM_MAIN", SRC, "-o", exe], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = column_shim_lib.sanitized("span")
     assert r.returncode == 0 and b"shapes ok" in r.stdout and not r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-2000:])

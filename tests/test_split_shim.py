@@ -5,19 +5,14 @@ the kept bytes before q: a kept byte gives out[kp] = in[q - a - b - l], B number
 number i gives piece_off[a + i + 1] = kp and list_off[i + 1] = a + i + 1; entry 0 of both arrays is stored by tile 0 alone,
 every other byte and word once, by the lane that owns its framed byte."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 
+import column_shim_lib
+
 from test_span_shim import A, B, DOT, KINDS, NL, UNSTORED, texts
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "split_shim.cpp")
-HDR = os.path.join(os.path.dirname(HERE), "trre_amd", "csrc", "records_block.hpp")
-SO = os.path.join(HERE, "_shim", "libsplit_shim.so")
-DEPS = [SRC, HDR, os.path.join(os.path.dirname(HDR), "scan_block.hpp")]
 GEOS = (0, 1, 2, 3)
 UNSTORED_BYTE = 0xEE
 FAR = dict(ra0=(1 << 32) + 5, rl0=(1 << 33) + 7, rk0=(1 << 34) + 11)
@@ -28,10 +23,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not (os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in DEPS)):
-            os.makedirs(os.path.dirname(SO), exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", SRC, "-o", SO], check=True)
-        L = ctypes.CDLL(SO)
+        L = column_shim_lib.load("split")
         vp, i64 = ctypes.c_void_p, ctypes.c_int64
         L.shim_split_tile.argtypes = [ctypes.c_int]
         L.shim_split_tile.restype = i64

@@ -2394,6 +2394,55 @@ static int str_unframe_located(ScanCtx* cx, const uint8_t* framed, int64_t m, ui
     return TRRE_OK;
 }
 
+// k_chunk_scan over each of `count` arrays, cnt [count][tiles] into base [count][tiles + 1], and the totals' read-backs queued
+// into tot: the caller synchronises
+static int scan_counts(const uint64_t* cnt, const uint64_t* base, int count, int64_t tiles, hipStream_t s, uint64_t* tot) {
+    for (int k = 0; k < count; ++k) {
+        uint64_t* b = const_cast<uint64_t*>(base) + k * (tiles + 1);
+        trre::launch_chunk_scan(cnt + k * tiles, b, tiles, s);
+        HIP_TRY(hipMemcpyAsync(&tot[k], b + tiles, 8, hipMemcpyDeviceToHost, s));
+    }
+    return TRRE_OK;
+}
+
+// ---- what the column calls' entry points share ----------------------------------------------------------------------------
+struct Range { const void* p; size_t bytes; };
+// a range of `more` overlaps one of `have` or another of `more` (the pairs within `have` are the caller's: d_in == d_out may be
+// a scan in place)
+static bool any_overlap(std::initializer_list<Range> have, std::initializer_list<Range> more) {
+    for (const Range* a = more.begin(); a != more.end(); ++a) {
+        for (const Range& h : have)
+            if (ranges_overlap(a->p, a->bytes, h.p, h.bytes)) return true;
+        for (const Range* b = a + 1; b != more.end(); ++b)
+            if (ranges_overlap(a->p, a->bytes, b->p, b->bytes)) return true;
+    }
+    return false;
+}
+
+// the program of the span, split, filter and field calls; `noun`: what the refusing call makes
+static int spans_program(const trre_prog* p, const char* noun) {
+    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, std::string("error: ") + noun + " take a program compiled with TRRE_MODE_SPANS");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    return TRRE_OK;
+}
+
+// The prog's state on the current device, locked until the call returns — one column call at a time per (prog, device) —, and
+// no split-form scan in flight.  inner: the find call's inner program, reached through that call only: the outer lock covers it.
+struct ColumnCall {
+    DeviceState* st = nullptr;
+    DeviceState* inner = nullptr;
+    std::unique_lock<std::mutex> lock;
+    int begin(trre_prog* p, trre_prog* inner_prog = nullptr) {
+        int rc = current_state(p, &st);
+        if (!rc && inner_prog) rc = current_state(inner_prog, &inner);
+        if (rc) return rc;
+        lock = std::unique_lock<std::mutex>(st->mu);
+        if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
+        return TRRE_OK;
+    }
+};
+
 // ---- ragged records (records_block.hpp) ----------------------------------------------------------------------------------
 static int records_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint8_t* d_out,
                       size_t cap, int64_t* d_out_off, size_t* out_len, hipStream_t s) {
@@ -2462,15 +2511,11 @@ int trre_scan_device_records(trre_prog* p, const uint8_t* d_in, size_t n, const 
     if (nrec >= ((size_t)1 << 58) || n >= ((size_t)1 << 56)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     const size_t ob = (nrec + 1) * 8;
-    if (ranges_overlap(d_off, ob, d_out_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
-        ranges_overlap(d_out_off, ob, d_in, n) || ranges_overlap(d_out_off, ob, d_out, cap))
+    if (any_overlap({{d_in, n}, {d_out, cap}}, {{d_off, ob}, {d_out_off, ob}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or the other offsets array");
-    DeviceState* st;
-    int rc = current_state(p, &st);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return records_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return records_on(p, c.st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
 }
 
 // ---- packed strings (records_block.hpp) ------------------------------------------------------------------------------------
@@ -2530,15 +2575,11 @@ int trre_scan_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     const size_t ob = (nrec + 1) * 8;
-    if (ranges_overlap(d_off, ob, d_out_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
-        ranges_overlap(d_out_off, ob, d_in, n) || ranges_overlap(d_out_off, ob, d_out, cap))
+    if (any_overlap({{d_in, n}, {d_out, cap}}, {{d_off, ob}, {d_out_off, ob}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or the other offsets array");
-    DeviceState* st;
-    int rc = current_state(p, &st);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return strings_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return strings_on(p, c.st, d_in, n, d_off, nrec, d_out, cap, d_out_off, out_len, static_cast<hipStream_t>(stream));
 }
 
 // ---- matched strings (records_block.hpp) -----------------------------------------------------------------------------------
@@ -2638,18 +2679,13 @@ int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (reinterpret_cast<uintptr_t>(d_valid) & 7u) return fail(TRRE_E_ARG, "error: the validity bitmap must be 8-byte aligned (it is written as 64-bit words)");
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     const size_t ob = (nrec + 1) * 8, vb = (nrec + 63) / 64 * 8;
-    if (ranges_overlap(d_off, ob, d_out_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
-        ranges_overlap(d_out_off, ob, d_in, n) || ranges_overlap(d_out_off, ob, d_out, cap))
+    if (any_overlap({{d_in, n}, {d_out, cap}}, {{d_off, ob}, {d_out_off, ob}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or the other offsets array");
-    if (ranges_overlap(d_valid, vb, d_in, n) || ranges_overlap(d_valid, vb, d_out, cap) || ranges_overlap(d_valid, vb, d_off, ob) ||
-        ranges_overlap(d_valid, vb, d_out_off, ob))
+    if (any_overlap({{d_in, n}, {d_out, cap}, {d_off, ob}, {d_out_off, ob}}, {{d_valid, vb}}))
         return fail(TRRE_E_ARG, "error: the validity bitmap overlaps the data or an offsets array");
-    DeviceState* st;
-    int rc = current_state(p, &st);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return match_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_matched, out_len,
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return match_on(p, c.st, d_in, n, d_off, nrec, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_matched, out_len,
                     static_cast<hipStream_t>(stream));
 }
 
@@ -2765,17 +2801,11 @@ int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || match_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     if (device_overlap(d_in, n, d_out, cap)) return TRRE_E_ARG;
     const size_t ob = (nrec + 1) * 8, mb = d_match_off ? (match_cap + 1) * 8 : 0;
-    if (ranges_overlap(d_off, ob, d_list_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cap) ||
-        ranges_overlap(d_list_off, ob, d_in, n) || ranges_overlap(d_list_off, ob, d_out, cap) || ranges_overlap(d_match_off, mb, d_in, n) ||
-        ranges_overlap(d_match_off, mb, d_out, cap) || ranges_overlap(d_match_off, mb, d_off, ob) || ranges_overlap(d_match_off, mb, d_list_off, ob))
+    if (any_overlap({{d_in, n}, {d_out, cap}}, {{d_off, ob}, {d_list_off, ob}, {d_match_off, mb}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
-    DeviceState *st, *stm;
-    int rc = current_state(p, &st);
-    if (!rc) rc = current_state(p->find_marks.get(), &stm);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);              // (the inner program is reached through this call only: the outer lock covers it)
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return find_on(p, st, stm, d_in, n, d_off, nrec, d_out, cap, d_match_off, match_cap, d_list_off, n_matches, out_len, static_cast<hipStream_t>(stream));
+    ColumnCall c;
+    if (const int rc = c.begin(p, p->find_marks.get())) return rc;
+    return find_on(p, c.st, c.inner, d_in, n, d_off, nrec, d_out, cap, d_match_off, match_cap, d_list_off, n_matches, out_len, static_cast<hipStream_t>(stream));
 }
 
 // ---- match spans and split strings (records_block.hpp) ---------------------------------------------------------------------
@@ -2832,11 +2862,8 @@ static int span_marks(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t
     pa.cnt = reinterpret_cast<uint64_t*>(c.part) + 1; pa.base = pa.cnt + 3 * ftiles;
     launch_span_count(pa, s);
     uint64_t tot[3] = {0, 0, 0};
-    for (int k = 0; k < 3; ++k) {
-        uint64_t* base = const_cast<uint64_t*>(pa.base) + k * (ftiles + 1);
-        launch_chunk_scan(pa.cnt + k * ftiles, base, ftiles, s);
-        HIP_TRY(hipMemcpyAsync(&tot[k], base + ftiles, 8, hipMemcpyDeviceToHost, s));
-    }
+    rc = scan_counts(pa.cnt, pa.base, 3, ftiles, s, tot);
+    if (rc) return rc;
     if (kept) {
         out->kcnt = const_cast<uint64_t*>(pa.base) + 3 * (ftiles + 1); out->kbase = out->kcnt + ftiles;
         SplitArgs ka{};
@@ -2880,22 +2907,14 @@ int trre_span_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     g_scan_flags = 0;
     if (n_matches) *n_matches = 0;
     if (!p || !d_off || !d_list_off || (n && !d_in) || (span_cap && (!d_start || !d_end))) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: match spans take a program compiled with TRRE_MODE_SPANS");
-    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
-        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (int rc = spans_program(p, "match spans")) return rc;
     if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || span_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     const size_t ob = (nrec + 1) * 8, sb = d_start ? span_cap * 8 : 0, eb = d_end ? span_cap * 8 : 0;
-    if (ranges_overlap(d_off, ob, d_list_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_list_off, ob, d_in, n) ||
-        ranges_overlap(d_start, sb, d_in, n) || ranges_overlap(d_start, sb, d_off, ob) || ranges_overlap(d_start, sb, d_list_off, ob) ||
-        ranges_overlap(d_end, eb, d_in, n) || ranges_overlap(d_end, eb, d_off, ob) || ranges_overlap(d_end, eb, d_list_off, ob) ||
-        ranges_overlap(d_start, sb, d_end, eb))
+    if (any_overlap({{d_in, n}}, {{d_off, ob}, {d_list_off, ob}, {d_start, sb}, {d_end, eb}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
-    DeviceState* st;
-    const int rc = current_state(p, &st);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return span_on(p, st, d_in, n, d_off, nrec, d_start, d_end, span_cap, d_list_off, n_matches, static_cast<hipStream_t>(stream));
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return span_on(p, c.st, d_in, n, d_off, nrec, d_start, d_end, span_cap, d_list_off, n_matches, static_cast<hipStream_t>(stream));
 }
 
 // the pieces between the matches: steps 1 - 5 are the span call's, with the kept bytes counted in front of the read-back
@@ -2931,22 +2950,37 @@ int trre_split_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (out_len) *out_len = 0;
     if (n_pieces) *n_pieces = 0;
     if (!p || !d_off || !d_list_off || (n && !d_in) || (cap && !d_out) || (piece_cap && !d_piece_off)) return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: split strings take a program compiled with TRRE_MODE_SPANS");
-    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
-        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (int rc = spans_program(p, "split strings")) return rc;
     if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || piece_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     const size_t ob = (nrec + 1) * 8, pb = d_piece_off ? (piece_cap + 1) * 8 : 0, cb = d_out ? cap : 0;
     if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the pieces are not made in place)");
-    if (ranges_overlap(d_off, ob, d_list_off, ob) || ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cb) ||
-        ranges_overlap(d_list_off, ob, d_in, n) || ranges_overlap(d_list_off, ob, d_out, cb) || ranges_overlap(d_piece_off, pb, d_in, n) ||
-        ranges_overlap(d_piece_off, pb, d_out, cb) || ranges_overlap(d_piece_off, pb, d_off, ob) || ranges_overlap(d_piece_off, pb, d_list_off, ob))
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_list_off, ob}, {d_piece_off, pb}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
-    DeviceState* st;
-    const int rc = current_state(p, &st);
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return split_on(p, c.st, d_in, n, d_off, nrec, d_out, cap, d_piece_off, piece_cap, d_list_off, n_pieces, out_len, static_cast<hipStream_t>(stream));
+}
+
+// What the filter call and the field call do with the span call's marks: the list offsets, and nothing else of the span call
+// (k_span_emit, lists only), into the library's own array; the geometry of the INPUT's tiles; the field call's bounds (field: its
+// arguments, *a their .f), which read the span call's tiles; then d_rec carved for the input's tiles — behind the status word:
+// part [tiles + 1], cnt [2][tiles], base [2][tiles + 1] — into *a
+static int filter_tiles(ScanCtx* cx, trre::SpanArgs& pa, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, hipStream_t s,
+                        trre::FilterArgs* a, const trre::FieldArgs* field) {
+    HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
+    pa.start = pa.end = nullptr; pa.list_off = cx->d_filter_lists; pa.n_match = 0; pa.lists_only = 1u;
+    trre::launch_span_emit(pa, s);
+    const int64_t T = trre::str_tile_bytes();
+    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
+    const int64_t tiles = std::max<int64_t>((a0 + (int64_t)n + T - 1) / T, 1);
+    a->in_v0 = d_in - a0; a->vbeg = a0; a->n = (int64_t)n; a->off = d_off; a->loff = cx->d_filter_lists; a->nrec = (int64_t)nrec;
+    a->tiles = tiles;
+    if (field) trre::launch_field_bounds(pa, *field, s);
+    RecCarve c;                                             // (room as for 2 tiles + 1: 6 tiles + 6 words)
+    const int rc = rec_carve(cx, 2 * tiles + 1, &c);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return split_on(p, st, d_in, n, d_off, nrec, d_out, cap, d_piece_off, piece_cap, d_list_off, n_pieces, out_len, static_cast<hipStream_t>(stream));
+    a->part = c.part; a->cnt = reinterpret_cast<uint64_t*>(c.part) + tiles + 1; a->base = a->cnt + 2 * tiles;
+    return TRRE_OK;
 }
 
 // the strings with a match (without one: TRRE_FILTER_INVERT), whole, and their rows: steps 1 - 5 are the span call's
@@ -2962,30 +2996,16 @@ static int filter_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t 
         HIP_TRY(hipStreamSynchronize(s));
         return TRRE_OK;
     }
-    // 6. the span call's list offsets, and nothing else of it, into the library's own array: the verdicts
-    HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
-    SpanArgs& pa = mk.pa;
-    pa.start = pa.end = nullptr; pa.list_off = cx->d_filter_lists; pa.n_match = 0; pa.lists_only = 1u;
-    launch_span_emit(pa, s);
-    // 7. over tiles of the INPUT: the first string of every tile, the kept strings and bytes per tile and before it (behind the
-    //    status word: part [tiles + 1], cnt [2][tiles], base [2][tiles + 1]); the two totals in one read-back
-    const int64_t T = str_tile_bytes();
-    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    const int64_t tiles = std::max<int64_t>((a0 + (int64_t)n + T - 1) / T, 1);
-    RecCarve c;                                             // (room as for 2 tiles + 1: 6 tiles + 6 words)
-    rc = rec_carve(cx, 2 * tiles + 1, &c);
-    if (rc) return rc;
+    // 6. the verdicts: the span call's list offsets; 7. over tiles of the INPUT: the first string of every tile, the kept strings
+    //    and bytes per tile and before it; the two totals in one read-back
     FilterArgs a{};
-    a.in_v0 = d_in - a0; a.vbeg = a0; a.n = (int64_t)n; a.off = d_off; a.loff = cx->d_filter_lists; a.nrec = (int64_t)nrec;
-    a.invert = (flags & TRRE_FILTER_INVERT) ? 1u : 0u; a.tiles = tiles;
-    a.part = c.part; a.cnt = reinterpret_cast<uint64_t*>(c.part) + tiles + 1; a.base = a.cnt + 2 * tiles;
+    a.invert = (flags & TRRE_FILTER_INVERT) ? 1u : 0u;
+    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a, nullptr);
+    if (rc) return rc;
     launch_filter_count(a, s);
     uint64_t tot[2] = {0, 0};
-    for (int k = 0; k < 2; ++k) {
-        uint64_t* base = const_cast<uint64_t*>(a.base) + k * (tiles + 1);
-        launch_chunk_scan(a.cnt + k * tiles, base, tiles, s);
-        HIP_TRY(hipMemcpyAsync(&tot[k], base + tiles, 8, hipMemcpyDeviceToHost, s));
-    }
+    rc = scan_counts(a.cnt, a.base, 2, a.tiles, s, tot);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     if (tot[0] > nrec || tot[1] > n) return fail(TRRE_E_DEVICE, "error: the kept strings do not add up (internal)");
@@ -3012,22 +3032,15 @@ int trre_filter_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, cons
     if (n_kept) *n_kept = 0;
     if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (row_cap && (!d_out_off || !d_rows))) return fail(TRRE_E_ARG, "error: null argument");
     if (flags & ~TRRE_FILTER_INVERT) return fail(TRRE_E_ARG, "error: unknown flag (TRRE_FILTER_INVERT is the only one)");
-    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: filtered strings take a program compiled with TRRE_MODE_SPANS");
-    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
-        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (int rc = spans_program(p, "filtered strings")) return rc;
     if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || row_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     const size_t ob = (nrec + 1) * 8, pb = d_out_off ? (row_cap + 1) * 8 : 0, rb = d_rows ? row_cap * 8 : 0, cb = d_out ? cap : 0;
     if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the kept strings are not made in place)");
-    if (ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cb) || ranges_overlap(d_out_off, pb, d_in, n) ||
-        ranges_overlap(d_out_off, pb, d_out, cb) || ranges_overlap(d_out_off, pb, d_off, ob) || ranges_overlap(d_rows, rb, d_in, n) ||
-        ranges_overlap(d_rows, rb, d_out, cb) || ranges_overlap(d_rows, rb, d_off, ob) || ranges_overlap(d_rows, rb, d_out_off, pb))
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_out_off, pb}, {d_rows, rb}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
-    DeviceState* st;
-    const int rc = current_state(p, &st);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return filter_on(p, st, d_in, n, d_off, nrec, flags, d_out, cap, d_out_off, d_rows, row_cap, n_kept, out_len, static_cast<hipStream_t>(stream));
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return filter_on(p, c.st, d_in, n, d_off, nrec, flags, d_out, cap, d_out_off, d_rows, row_cap, n_kept, out_len, static_cast<hipStream_t>(stream));
 }
 
 // field k of every string: steps 1 - 6 are the filter call's
@@ -3043,35 +3056,19 @@ static int field_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n
         HIP_TRY(hipStreamSynchronize(s));
         return TRRE_OK;
     }
-    // 6. the span call's list offsets, and nothing else of it, into the library's own array
-    HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
+    // 6. the span call's list offsets; 7. the bitmap, and where every field starts and ends: from the offsets and the list offsets,
+    //    and from the framed text's markers — before the carve: it reads the span call's tiles, which the carve reuses
     HIP_TRY(cx->d_field_bounds.reserve(nrec, 2 * nrec * 8));
-    SpanArgs& pa = mk.pa;
-    pa.start = pa.end = nullptr; pa.list_off = cx->d_filter_lists; pa.n_match = 0; pa.lists_only = 1u;
-    launch_span_emit(pa, s);
-    // 7. the bitmap, and where every field starts and ends: from the offsets and the list offsets, and from the framed text's markers
-    const int64_t T = str_tile_bytes();
-    const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    const int64_t tiles = std::max<int64_t>((a0 + (int64_t)n + T - 1) / T, 1);
     FieldArgs a{};
-    a.f.in_v0 = d_in - a0; a.f.vbeg = a0; a.f.n = (int64_t)n; a.f.off = d_off; a.f.loff = cx->d_filter_lists; a.f.nrec = (int64_t)nrec;
-    a.f.tiles = tiles;
     a.k = k; a.lo = cx->d_field_bounds; a.hi = a.lo + nrec; a.valid = d_valid; a.words = (int64_t)((nrec + 63) / 64);
-    launch_field_bounds(pa, a, s);
-    // 8. over tiles of the INPUT: the first string of every tile, the strings with the field and the field bytes per tile and before
-    //    it (behind the status word: part [tiles + 1], cnt [2][tiles], base [2][tiles + 1]; the span call's tiles, which step 7 read,
-    //    are done with); the two totals in one read-back
-    RecCarve c;                                             // (room as for 2 tiles + 1: 6 tiles + 6 words)
-    rc = rec_carve(cx, 2 * tiles + 1, &c);
+    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a.f, &a);
     if (rc) return rc;
-    a.f.part = c.part; a.f.cnt = reinterpret_cast<uint64_t*>(c.part) + tiles + 1; a.f.base = a.f.cnt + 2 * tiles;
+    // 8. over tiles of the INPUT: the first string of every tile, the strings with the field and the field bytes per tile and before
+    //    it; the two totals in one read-back
     launch_field_count(a, s);
     uint64_t tot[2] = {0, 0};
-    for (int x = 0; x < 2; ++x) {
-        uint64_t* base = const_cast<uint64_t*>(a.f.base) + x * (tiles + 1);
-        launch_chunk_scan(a.f.cnt + x * tiles, base, tiles, s);
-        HIP_TRY(hipMemcpyAsync(&tot[x], base + tiles, 8, hipMemcpyDeviceToHost, s));
-    }
+    rc = scan_counts(a.f.cnt, a.f.base, 2, a.f.tiles, s, tot);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     if (tot[0] > nrec || tot[1] > n) return fail(TRRE_E_DEVICE, "error: the fields do not add up (internal)");
@@ -3096,25 +3093,18 @@ int trre_field_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (n_valid) *n_valid = 0;
     if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (!d_out_off && (d_out || cap)) || (nrec && !d_valid))
         return fail(TRRE_E_ARG, "error: null argument");
-    if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, "error: field strings take a program compiled with TRRE_MODE_SPANS");
-    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
-        return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (int rc = spans_program(p, "field strings")) return rc;
     if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
     if (reinterpret_cast<uintptr_t>(d_valid) & 7u) return fail(TRRE_E_ARG, "error: the validity bitmap must be 8-byte aligned (it is written as 64-bit words)");
     const size_t ob = (nrec + 1) * 8, pb = d_out_off ? ob : 0, vb = (nrec + 63) / 64 * 8, cb = d_out ? cap : 0;
     if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the fields are not made in place)");
-    if (ranges_overlap(d_off, ob, d_in, n) || ranges_overlap(d_off, ob, d_out, cb) || ranges_overlap(d_out_off, pb, d_in, n) ||
-        ranges_overlap(d_out_off, pb, d_out, cb) || ranges_overlap(d_out_off, pb, d_off, ob))
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_out_off, pb}}))
         return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
-    if (ranges_overlap(d_valid, vb, d_in, n) || ranges_overlap(d_valid, vb, d_out, cb) || ranges_overlap(d_valid, vb, d_off, ob) ||
-        ranges_overlap(d_valid, vb, d_out_off, pb))
+    if (any_overlap({{d_in, n}, {d_out, cb}, {d_off, ob}, {d_out_off, pb}}, {{d_valid, vb}}))
         return fail(TRRE_E_ARG, "error: the validity bitmap overlaps the data or an offsets array");
-    DeviceState* st;
-    const int rc = current_state(p, &st);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->ctx.pend.active) return fail(TRRE_E_ARG, "error: a split-form scan is still in flight on this device: call trre_scan_finish first");
-    return field_on(p, st, d_in, n, d_off, nrec, k, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_valid, out_len,
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return field_on(p, c.st, d_in, n, d_off, nrec, k, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_valid, out_len,
                     static_cast<hipStream_t>(stream));
 }
 

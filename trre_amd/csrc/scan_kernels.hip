@@ -1528,6 +1528,24 @@ __device__ __forceinline__ uint32_t rec_block_scan(uint32_t s, uint32_t* pre, ui
     return total;
 }
 
+// The workgroup's totals of N counts per thread: cnt[x * tiles + b] = the sum of c[x] over the threads, x < N.  Lane 0 of every wave
+// stores the wave's sums into an array of the helper's own (E: the width a wave's sum keeps), a barrier, and thread x adds them.
+template <class E, int N>
+__device__ __forceinline__ void tile_totals(const uint64_t (&c)[N], uint64_t* cnt, int64_t tiles, int64_t b) {
+    __shared__ E wsum[N][RG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    for (int x = 0; x < N; ++x) {
+        const uint64_t s = wave_sum(c[x]);
+        if ((tid & (kWave - 1)) == 0) wsum[x][tid / kWave] = (E)s;
+    }
+    __syncthreads();
+    if (tid < N) {
+        uint64_t t = 0;
+        for (int k = 0; k < RG::THREADS / kWave; ++k) t += wsum[tid][k];
+        cnt[(int64_t)tid * tiles + b] = t;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_rec_check(const int64_t* off, int64_t nrec, int64_t n, uint32_t* status) {
     uint32_t bad = 0;
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -1569,15 +1587,8 @@ __global__ __launch_bounds__(256) void k_rec_rank(RecArgs a) {
 }
 
 __global__ __launch_bounds__(RG::THREADS) void k_rec_count(RecArgs a) {
-    __shared__ uint32_t wtot[RG::THREADS / kWave];
-    const uint64_t c = wave_sum(rec_count_vecs<RG>(a, blockIdx.x, threadIdx.x, nullptr));
-    if ((threadIdx.x & (kWave - 1)) == 0) wtot[threadIdx.x / kWave] = (uint32_t)c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int k = 0; k < RG::THREADS / kWave; ++k) t += wtot[k];
-        a.cnt[blockIdx.x] = t;
-    }
+    const uint64_t c[1] = {rec_count_vecs<RG>(a, blockIdx.x, threadIdx.x, nullptr)};
+    tile_totals<uint32_t>(c, a.cnt, 0, blockIdx.x);
 }
 
 __global__ __launch_bounds__(RG::THREADS) void k_rec_locate(RecArgs a, uint32_t* status) {
@@ -1638,7 +1649,12 @@ __global__ __launch_bounds__(256) void k_str_rank(StrArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.nrec; i += stride) str_add_base(a, SG::TILE, i);
 }
 
-__global__ __launch_bounds__(SG::THREADS) void k_str_unframe(StrArgs a) {
+// A framed tile without its marked bytes into its place: what k_str_unframe, k_match_unframe and k_find_unframe share, written
+// once.  mark(t, tid, w, bits32) leaves the tile's marks, with whatever barrier its own stores need between them; the body's
+// barriers: behind the marks and the byte image, which every later step reads across threads; the scan's own between pre and
+// str_fill_pv; one behind pv — behind_prefixes(t, tid, bits16, pv) runs there and only reads —; one behind inv.
+template <class M, class F>
+__device__ __forceinline__ void str_unframe_tile(const StrArgs& a, M mark, F behind_prefixes) {
     __shared__ U128 lds[SG::NVEC + 2];
     __shared__ uint32_t bits32[SG::NVEC / 2];
     __shared__ uint32_t pv[SG::NVEC + 1];
@@ -1649,19 +1665,32 @@ __global__ __launch_bounds__(SG::THREADS) void k_str_unframe(StrArgs a) {
     const StrTile<SG> t(a, blockIdx.x, false);
     U128 w[SG::VECS + 1];
     str_load_vecs<SG>(a, t, tid, w);
-    for (int k = tid; k < SG::NVEC / 2; k += SG::THREADS) bits32[k] = 0;
-    __syncthreads();
-    str_mark<SG>(a, t, tid, bits32, false);
+    mark(t, tid, w, bits32);
     str_keep_vecs<SG>(t, tid, w, lds);
     __syncthreads();
     const uint16_t* bits16 = reinterpret_cast<const uint16_t*>(bits32);
     const uint32_t marks = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
     str_fill_pv<SG>(bits16, pre[tid], tid, pv);
     __syncthreads();
+    behind_prefixes(t, tid, bits16, pv);
     const StrOut<SG> o(a, t, marks);
     str_fill_inv<SG>(t, o, tid, bits16, pv, inv);
     __syncthreads();
     str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
+}
+using StrRegs = U128 (&)[SG::VECS + 1];
+// the marks from the bytes (the match and find calls)
+__device__ __forceinline__ void unframe_mark_bytes(const StrTile<SG>& t, int tid, StrRegs w, uint32_t* bits32) {
+    match_mark_vecs<SG>(t, tid, w, reinterpret_cast<uint16_t*>(bits32));
+}
+
+// the marks from the located offsets: the image zeroed, a barrier, then the XORs
+__global__ __launch_bounds__(SG::THREADS) void k_str_unframe(StrArgs a) {
+    str_unframe_tile(a, [&](const StrTile<SG>& t, int tid, StrRegs, uint32_t* bits32) {
+        for (int k = tid; k < SG::NVEC / 2; k += SG::THREADS) bits32[k] = 0;
+        __syncthreads();
+        str_mark<SG>(a, t, tid, bits32, false);
+    }, [](const StrTile<SG>&, int, const uint16_t*, const uint32_t*) {});
 }
 
 unsigned rec_grid(int64_t items) {
@@ -1717,41 +1746,14 @@ __global__ __launch_bounds__(256) void k_match_final(MatchArgs a) {
 
 // '\n' per tile of the compaction (k_rec_count on the strings' 16 KiB tiles)
 __global__ __launch_bounds__(SG::THREADS) void k_match_count(RecArgs a) {
-    __shared__ uint32_t wtot[SG::THREADS / kWave];
-    const uint64_t c = wave_sum(rec_count_vecs<SG>(a, blockIdx.x, threadIdx.x, nullptr));
-    if ((threadIdx.x & (kWave - 1)) == 0) wtot[threadIdx.x / kWave] = (uint32_t)c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int k = 0; k < SG::THREADS / kWave; ++k) t += wtot[k];
-        a.cnt[blockIdx.x] = t;
-    }
+    const uint64_t c[1] = {rec_count_vecs<SG>(a, blockIdx.x, threadIdx.x, nullptr)};
+    tile_totals<uint32_t>(c, a.cnt, 0, blockIdx.x);
 }
 
 // k_str_unframe with the marks from the bytes: a.part holds the '\n' before every tile, so a tile's destination starts at
 // s0 - part[b], and no offset is touched
 __global__ __launch_bounds__(SG::THREADS) void k_match_unframe(StrArgs a) {
-    __shared__ U128 lds[SG::NVEC + 2];
-    __shared__ uint32_t bits32[SG::NVEC / 2];
-    __shared__ uint32_t pv[SG::NVEC + 1];
-    __shared__ uint16_t inv[SG::NVEC + 2];
-    __shared__ uint32_t pre[SG::THREADS];
-    __shared__ uint32_t wtot[SG::THREADS / kWave];
-    const int tid = threadIdx.x;
-    const StrTile<SG> t(a, blockIdx.x, false);
-    U128 w[SG::VECS + 1];
-    str_load_vecs<SG>(a, t, tid, w);
-    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
-    match_mark_vecs<SG>(t, tid, w, bits16);
-    str_keep_vecs<SG>(t, tid, w, lds);
-    __syncthreads();
-    const uint32_t marks = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
-    str_fill_pv<SG>(bits16, pre[tid], tid, pv);
-    __syncthreads();
-    const StrOut<SG> o(a, t, marks);
-    str_fill_inv<SG>(t, o, tid, bits16, pv, inv);
-    __syncthreads();
-    str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
+    str_unframe_tile(a, unframe_mark_bytes, [](const StrTile<SG>&, int, const uint16_t*, const uint32_t*) {});
 }
 
 // ---- found strings (records_block.hpp; runtime.cpp: trre_find_device_strings) ----------------------------------------------
@@ -1761,47 +1763,18 @@ static_assert(SG::THREADS % kWave == 0 && SG::NVEC % 4 == 0, "find_offset_vecs: 
 // is match_off and a.nrec the number of matches.  The tile's bytes and marks are staged into LDS by all threads; the barriers
 // of the compaction stand between that and every read here (pv is complete behind the second one).
 __global__ __launch_bounds__(SG::THREADS) void k_find_unframe(StrArgs a) {
-    __shared__ U128 lds[SG::NVEC + 2];
-    __shared__ uint32_t bits32[SG::NVEC / 2];
-    __shared__ uint32_t pv[SG::NVEC + 1];
-    __shared__ uint16_t inv[SG::NVEC + 2];
-    __shared__ uint32_t pre[SG::THREADS];
-    __shared__ uint32_t wtot[SG::THREADS / kWave];
-    const int tid = threadIdx.x;
-    const StrTile<SG> t(a, blockIdx.x, false);
-    U128 w[SG::VECS + 1];
-    str_load_vecs<SG>(a, t, tid, w);
-    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
-    match_mark_vecs<SG>(t, tid, w, bits16);
-    str_keep_vecs<SG>(t, tid, w, lds);
-    __syncthreads();
-    const uint32_t marks = rec_block_scan(rec_seg_count<SG>(bits16, tid), pre, wtot);
-    str_fill_pv<SG>(bits16, pre[tid], tid, pv);
-    __syncthreads();
-    find_offset_vecs<SG>(a, t, tid, bits16, pv);
-    const StrOut<SG> o(a, t, marks);
-    str_fill_inv<SG>(t, o, tid, bits16, pv, inv);
-    __syncthreads();
-    str_unframe_vecs<SG>(a, t, o, tid, lds, bits16, pv, inv);
+    str_unframe_tile(a, unframe_mark_bytes, [&](const StrTile<SG>& t, int tid, const uint16_t* bits16, const uint32_t* pv) {
+        find_offset_vecs<SG>(a, t, tid, bits16, pv);
+    });
 }
 
 // ---- match spans (records_block.hpp; runtime.cpp: trre_span_device_strings) -------------------------------------------------
 // A, B and '\n' per framed tile
 __global__ __launch_bounds__(SG::THREADS) void k_span_count(SpanArgs a) {
-    __shared__ uint32_t wtot[3][SG::THREADS / kWave];
-    const int tid = threadIdx.x;
     uint32_t c[3] = {0u, 0u, 0u};
-    span_mark_vecs<SG>(a, blockIdx.x, tid, nullptr, c);
-    for (int x = 0; x < 3; ++x) {
-        const uint64_t s = wave_sum(c[x]);
-        if ((tid & (kWave - 1)) == 0) wtot[x][tid / kWave] = (uint32_t)s;
-    }
-    __syncthreads();
-    if (tid < 3) {
-        uint64_t t = 0;
-        for (int k = 0; k < SG::THREADS / kWave; ++k) t += wtot[tid][k];
-        a.cnt[(int64_t)tid * a.tiles + blockIdx.x] = t;
-    }
+    span_mark_vecs<SG>(a, blockIdx.x, threadIdx.x, nullptr, c);
+    const uint64_t c64[3] = {c[0], c[1], c[2]};
+    tile_totals<uint32_t>(c64, a.cnt, a.tiles, blockIdx.x);
 }
 
 // The tile's marks, their two workgroup scans and the prefixes, then f(b, tid, bits, pv_ab, pv_nl): what k_span_emit and
@@ -1840,7 +1813,7 @@ __global__ __launch_bounds__(SG::THREADS) void k_span_emit(SpanArgs a) {
 // ---- split strings (records_block.hpp; runtime.cpp: trre_split_device_strings) ---------------------------------------------
 // The kept bytes per framed tile.  The mark images are written by all threads and read across them (a thread's rank segment is
 // not the vectors it loaded): a barrier stands behind split_mark_vecs; the scan's own barriers stand between pre_ab and its
-// readers and between its use of wtot and the sums'.
+// readers; the sums go through tile_totals' array, not the scan's wtot.
 __global__ __launch_bounds__(SG::THREADS) void k_split_count(SplitArgs a) {
     __shared__ uint16_t bits[3 * SG::NVEC];
     __shared__ uint32_t pre_ab[SG::THREADS];
@@ -1852,14 +1825,8 @@ __global__ __launch_bounds__(SG::THREADS) void k_split_count(SplitArgs a) {
     uint32_t ab, nl;
     span_seg_count<SG>(bits, tid, ab, nl);
     rec_block_scan(ab, pre_ab, wtot);
-    const uint64_t s = wave_sum(split_seg_kept<SG>(a, b, tid, bits, pre_ab[tid], nullptr));
-    if ((tid & (kWave - 1)) == 0) wtot[tid / kWave] = (uint32_t)s;
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t t = 0;
-        for (int k = 0; k < SG::THREADS / kWave; ++k) t += wtot[k];
-        a.kcnt[b] = t;
-    }
+    const uint64_t kept[1] = {split_seg_kept<SG>(a, b, tid, bits, pre_ab[tid], nullptr)};
+    tile_totals<uint32_t>(kept, a.kcnt, 0, b);
 }
 
 // The pieces' bytes, where each piece starts and the list offsets.  Barriers: behind split_mark_vecs (the images are read across
@@ -1901,29 +1868,22 @@ __global__ __launch_bounds__(256) void k_filter_part(FilterArgs a) {
 
 // The kept strings that end in the tile and the tile's kept bytes, from the offsets and the list offsets alone.
 __global__ __launch_bounds__(FG::THREADS) void k_filter_count(FilterArgs a) {
-    __shared__ uint64_t wsum[2][FG::THREADS / kWave];
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const FilterTile<FG> t(a, b);
-    uint64_t rows, bytes;
-    filter_count_strings<FG>(a, t, tid, rows, bytes);
-    rows = wave_sum(rows);
-    bytes = wave_sum(bytes);
-    if ((tid & (kWave - 1)) == 0) { wsum[0][tid / kWave] = rows; wsum[1][tid / kWave] = bytes; }
-    __syncthreads();
-    if (tid < 2) {
-        uint64_t s = 0;
-        for (int k = 0; k < FG::THREADS / kWave; ++k) s += wsum[tid][k];
-        a.cnt[(int64_t)tid * a.tiles + b] = s;
-    }
+    uint64_t c[2];                                   // rows, bytes: 64-bit, 2^30 and more empty strings can end in one tile
+    filter_count_strings<FG>(a, FilterTile<FG>(a, blockIdx.x), threadIdx.x, c[0], c[1]);
+    tile_totals<uint64_t>(c, a.cnt, a.tiles, blockIdx.x);
 }
 
-// The kept strings' bytes, their rows and where each starts.  Barriers: behind the zeroing of the toggle image, before the XORs;
+// The compaction of the filter and field calls, written once: the kept strings' (the fields') bytes and, by store(t, b, tid,
+// bits16, pv), their rows and where each starts.  mark(t, tid, bits32) XORs the toggles into the zeroed image;
+// behind_image(t, tid, pre, wtot) runs behind the second barrier, is reached by every thread of the workgroup — it may scan — and
+// leaves pre and wtot free again.  Barriers: behind the zeroing of the toggle image, before the XORs;
 // behind the XORs and the byte image, which every later step reads across threads; the scans' own between pre and its readers
 // (a thread turns its own segment's toggles into kept bits in place: nobody else reads them in between); one more behind pv,
-// after which the image, pre and pv are only read.  A thread's rank among the tile's kept strings is the scan of the threads'
-// counts: 23 bits at a time when 2^30 strings or more end in one tile, so that no partial sum leaves 32 bits.
-__global__ __launch_bounds__(FG::THREADS) void k_filter_emit(FilterArgs a) {
+// after which the image, pre and pv are only read.  (The filter call's behind_image: a thread's rank among the tile's kept strings
+// is the scan of the threads' counts, 23 bits at a time when 2^30 strings or more end in one tile, so that no partial sum leaves
+// 32 bits.)
+template <class M, class R, class S>
+__device__ __forceinline__ void filter_emit_tile(const FilterArgs& a, M mark, R behind_image, S store) {
     __shared__ U128 lds[FG::NVEC + 2];
     __shared__ uint32_t bits32[FG::NVEC / 2];
     __shared__ uint32_t pv[FG::NVEC + 1];
@@ -1936,22 +1896,34 @@ __global__ __launch_bounds__(FG::THREADS) void k_filter_emit(FilterArgs a) {
     filter_load_vecs<FG>(a, t, tid, w);              // the tile's bytes are on their way while the strings are looked up
     for (int k = tid; k < FG::NVEC / 2; k += FG::THREADS) bits32[k] = 0;
     __syncthreads();
-    const uint64_t mine = filter_mark<FG>(a, t, tid, bits32);
+    mark(t, tid, bits32);
     filter_keep_vecs<FG>(tid, w, lds);
     __syncthreads();
-    rec_block_scan((uint32_t)(mine & 0x7fffffu), pre, wtot);
-    uint64_t r0 = pre[tid];
-    if (t.i1 - t.i0 >= ((int64_t)1 << 30)) {         // (the same for every thread of the workgroup)
-        rec_block_scan((uint32_t)(mine >> 23), pre, wtot);
-        r0 += (uint64_t)pre[tid] << 23;
-    }
+    behind_image(t, tid, pre, wtot);
     uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
     rec_block_scan(rec_seg_count<FG>(bits16, tid), pre, wtot);
     rec_block_scan(filter_seg_kept<FG>(a, t, tid, bits16, pre[tid]), pre, wtot);
     str_fill_pv<FG>(bits16, pre[tid], tid, pv);
     __syncthreads();
-    filter_emit_rows<FG>(a, t, b, tid, r0, bits16, pv);
+    store(t, b, tid, bits16, pv);
     filter_emit_vecs<FG>(a, b, tid, lds, bits16, pre, pv);
+}
+
+// The kept strings: filter_mark's toggles, the rows' ranks, filter_emit_rows' stores.
+__global__ __launch_bounds__(FG::THREADS) void k_filter_emit(FilterArgs a) {
+    uint64_t mine = 0, r0 = 0;
+    filter_emit_tile(a, [&](const FilterTile<FG>& t, int tid, uint32_t* bits32) { mine = filter_mark<FG>(a, t, tid, bits32); },
+                     [&](const FilterTile<FG>& t, int tid, uint32_t* pre, uint32_t* wtot) {
+                         rec_block_scan((uint32_t)(mine & 0x7fffffu), pre, wtot);
+                         r0 = pre[tid];
+                         if (t.i1 - t.i0 >= ((int64_t)1 << 30)) {         // (the same for every thread of the workgroup)
+                             rec_block_scan((uint32_t)(mine >> 23), pre, wtot);
+                             r0 += (uint64_t)pre[tid] << 23;
+                         }
+                     },
+                     [&](const FilterTile<FG>& t, int64_t b, int tid, const uint16_t* bits16, const uint32_t* pv) {
+                         filter_emit_rows<FG>(a, t, b, tid, r0, bits16, pv);
+                     });
 }
 
 // ---- field k of every string (records_block.hpp; runtime.cpp: trre_field_device_strings) ----------------------------------
@@ -1978,49 +1950,19 @@ __global__ __launch_bounds__(SG::THREADS) void k_field_pick(SpanArgs sp, FieldAr
 
 // The strings with the field that end in the tile and the tile's field bytes, from the offsets, the list offsets and the bounds.
 __global__ __launch_bounds__(FG::THREADS) void k_field_count(FieldArgs a) {
-    __shared__ uint64_t wsum[2][FG::THREADS / kWave];
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const FilterTile<FG> t(a.f, b);
-    uint64_t valid, bytes;
-    field_count_strings<FG>(a, t, tid, valid, bytes);
-    valid = wave_sum(valid);
-    bytes = wave_sum(bytes);
-    if ((tid & (kWave - 1)) == 0) { wsum[0][tid / kWave] = valid; wsum[1][tid / kWave] = bytes; }
-    __syncthreads();
-    if (tid < 2) {
-        uint64_t s = 0;
-        for (int k = 0; k < FG::THREADS / kWave; ++k) s += wsum[tid][k];
-        a.f.cnt[(int64_t)tid * a.f.tiles + b] = s;
-    }
+    uint64_t c[2];                                   // valid, bytes
+    field_count_strings<FG>(a, FilterTile<FG>(a.f, blockIdx.x), threadIdx.x, c[0], c[1]);
+    tile_totals<uint64_t>(c, a.f.cnt, a.f.tiles, blockIdx.x);
 }
 
-// The fields' bytes and where each starts: k_filter_emit with field_mark's toggles, and its barriers — behind the zeroing of the
-// toggle image, before the XORs; behind the XORs and the byte image; the scans' own between pre and its readers; one more behind
-// pv, after which the image, pre and pv are only read.
+// The fields' bytes and where each starts: the filter call's compaction (filter_emit_tile, and its barriers) with field_mark's
+// toggles and field_emit_offsets' stores.
 __global__ __launch_bounds__(FG::THREADS) void k_field_emit(FieldArgs a) {
-    __shared__ U128 lds[FG::NVEC + 2];
-    __shared__ uint32_t bits32[FG::NVEC / 2];
-    __shared__ uint32_t pv[FG::NVEC + 1];
-    __shared__ uint32_t pre[FG::THREADS];
-    __shared__ uint32_t wtot[FG::THREADS / kWave];
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const FilterTile<FG> t(a.f, b);
-    U128 w[FG::VECS];
-    filter_load_vecs<FG>(a.f, t, tid, w);            // the tile's bytes are on their way while the bounds are looked up
-    for (int k = tid; k < FG::NVEC / 2; k += FG::THREADS) bits32[k] = 0;
-    __syncthreads();
-    field_mark<FG>(a, t, tid, bits32);
-    filter_keep_vecs<FG>(tid, w, lds);
-    __syncthreads();
-    uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits32);
-    rec_block_scan(rec_seg_count<FG>(bits16, tid), pre, wtot);
-    rec_block_scan(filter_seg_kept<FG>(a.f, t, tid, bits16, pre[tid]), pre, wtot);
-    str_fill_pv<FG>(bits16, pre[tid], tid, pv);
-    __syncthreads();
-    field_emit_offsets<FG>(a, t, b, tid, bits16, pv);
-    filter_emit_vecs<FG>(a.f, b, tid, lds, bits16, pre, pv);
+    filter_emit_tile(a.f, [&](const FilterTile<FG>& t, int tid, uint32_t* bits32) { field_mark<FG>(a, t, tid, bits32); },
+                     [](const FilterTile<FG>&, int, uint32_t*, uint32_t*) {},
+                     [&](const FilterTile<FG>& t, int64_t b, int tid, const uint16_t* bits16, const uint32_t* pv) {
+                         field_emit_offsets<FG>(a, t, b, tid, bits16, pv);
+                     });
 }
 
 void launch_field_bounds(const SpanArgs& sp, const FieldArgs& a, void* stream) {
