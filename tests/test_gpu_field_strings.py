@@ -14,53 +14,22 @@ import filter_lib
 import span_lib
 import split_lib
 import trre_amd
-from span_lib import LAYOUTS, PAIRS, Spanner, pack
+from gpu_column_lib import (BFILL, FILL, PAD, assert_prefix, assert_untouched, bitmap_of, blob, carve, dev, lst, off_dev, pack, sequence,
+                            soup, to_dev, words)
+from span_lib import LAYOUTS, PAIRS, Spanner
 from test_gpu_filter_strings import POOL          # the filter tests' pool, NULs and empties in it
 from trre_amd import api
 
 pytestmark = pytest.mark.gpu
 
-FILL = -7
-BFILL = 0xA5
-PAD = 8
 KS = (0, 1, 2, -1, -2, 5, -(1 << 63))
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data, mis=0):
-    """the bytes on the device, at an address that is `mis` past a 16-byte boundary"""
-    import torch
-    t = torch.zeros(len(data) + 32, dtype=torch.uint8, device=dev())
-    at = (-t.data_ptr()) % 16 + mis
-    v = t[at:at + len(data)]
-    if data:
-        v.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
-    assert len(data) == 0 or v.data_ptr() % 16 == mis % 16
-    return v
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
-def words(n):
-    import torch
-    return torch.full((n,), FILL, dtype=torch.int64, device=dev())
 
 
 def raw(p, values, n, offsets, nrec, k, cap, null=False, out=None, ooff=None, valid=None, out_mis=0):
     """the C ABI itself, with sentinel-filled arrays: (rc, *n_valid, *out_len, d_out, d_out_off, d_valid as words); d_out lies
     `out_mis` past a 16-byte boundary; null: the size query, without d_out and d_out_off"""
-    import torch
     if out is None:
-        t = torch.full((cap + PAD + 32,), BFILL, dtype=torch.uint8, device=dev())
-        at = (-t.data_ptr()) % 16 + out_mis
-        out = t[at:at + cap + PAD]
+        out = carve(cap, out_mis)
     if ooff is None:
         ooff = words(nrec + 1 + PAD)
     if valid is None:
@@ -69,20 +38,6 @@ def raw(p, values, n, offsets, nrec, k, cap, null=False, out=None, ooff=None, va
     rc = api.lib().trre_field_device_strings(p._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, k, None if null else out.data_ptr(),
                                              cap, None if null else ooff.data_ptr(), valid.data_ptr(), ctypes.byref(v), ctypes.byref(m), None)
     return rc, v.value, m.value, out, ooff, valid
-
-
-def blob(t):
-    return t.cpu().numpy().tobytes()
-
-
-def lst(t):
-    return t.cpu().numpy().tolist()
-
-
-def bitmap_of(valid, nrec):
-    """the bitmap's bytes and what lies behind them, from the sentinel-filled words"""
-    nw = (nrec + 63) // 64
-    return blob(valid[:nw]), lst(valid[nw:])
 
 
 def check(p, spans, recs, label, ks=KS, mis=0, out_mis=0, pieces=None):
@@ -103,8 +58,8 @@ def check(p, spans, recs, label, ks=KS, mis=0, out_mis=0, pieces=None):
         assert blob(packed) == field_lib.bitmap(want[2]), (label, k)
         rc, v, m, out2, oo2, valid2 = raw(p, values, len(data), offsets, nrec, k, need, out_mis=out_mis)
         assert (rc, v, m) == (0, n_valid, need), (label, k, rc, v, m, api.lib().trre_last_error())
-        assert blob(out2[:need]) == want[0] and bool((out2[need:] == BFILL).all()), (label, k)
-        assert lst(oo2[:nrec + 1]) == want[1] and bool((oo2[nrec + 1:] == FILL).all()), (label, k)
+        assert_prefix(out2, want[0], (label, k))
+        assert_prefix(oo2, want[1], (label, k))
         assert bitmap_of(valid2, nrec) == (field_lib.bitmap(want[2]), [FILL] * PAD), (label, k)
         assert sum(bin(b).count("1") for b in bitmap_of(valid2, nrec)[0]) == v, (label, k)      # *n_valid is the bitmap's population
         if pieces is not None and k > -(1 << 62):
@@ -123,10 +78,6 @@ def device_split(p, recs, mis=0):
     data, off = pack(recs)
     out, po, lo = p.split_strings(to_dev(data, mis), off_dev(off))
     return blob(out), lst(po), lst(lo)
-
-
-def soup(rng, alphabet, n, longest=30):
-    return [bytes(rng.choice(alphabet) for _ in range(rng.randrange(0, longest))) for _ in range(n)]
 
 
 def test_paired_patterns_and_layouts():
@@ -224,7 +175,8 @@ def test_capacity_and_sizes():
 
         def refused(rc, v, m, out, oo, valid):
             assert (rc, v, m) == (api.E_CAPACITY, n_valid, need), (k, rc, v, m)
-            assert bool((out == BFILL).all()) and bool((oo == FILL).all()), k
+            assert_untouched(out, k)
+            assert_untouched(oo, k)
             assert bitmap_of(valid, nrec) == (field_lib.bitmap(want[2]), [FILL] * PAD), k
 
         refused(*raw(p, values, len(data), offsets, nrec, k, 0, null=True))
@@ -232,8 +184,8 @@ def test_capacity_and_sizes():
         refused(*raw(p, values, len(data), offsets, nrec, k, need - 1))
         rc, v, m, out, oo, valid = raw(p, values, len(data), offsets, nrec, k, need)
         assert (rc, v, m) == (0, n_valid, need), (k, rc, v, m)
-        assert blob(out[:need]) == want[0] and bool((out[need:] == BFILL).all()), k
-        assert lst(oo[:nrec + 1]) == want[1] and bool((oo[nrec + 1:] == FILL).all()), k
+        assert_prefix(out, want[0], k)
+        assert_prefix(oo, want[1], k)
         assert bitmap_of(valid, nrec) == (field_lib.bitmap(want[2]), [FILL] * PAD), k
 
 
@@ -246,8 +198,9 @@ def test_errors_touch_nothing():
     def untouched(rc_want, p, vals=values, offs=offsets, cap=700, k=1, **kw):
         rc, v, m, out, oo, valid = raw(p, vals, len(data), offs, 4, k, cap, **kw)
         assert rc == rc_want and (v, m) == (0, 0), (rc, v, m, api.lib().trre_last_error())
-        for name, t, fill in (("out", out, BFILL), ("ooff", oo, FILL), ("valid", valid, FILL)):
-            assert name in kw or bool((t == fill).all()), name
+        for name, t in (("out", out), ("ooff", oo), ("valid", valid)):
+            if name not in kw:
+                assert_untouched(t, name)
         assert lst(offsets) == off and blob(values) == data
 
     for mode in ("scan", "match", "find"):
@@ -281,7 +234,8 @@ def test_errors_touch_nothing():
         holed[at] = 10
         rc, v, m, out, oo, valid = raw(p, to_dev(bytes(holed)), len(data), offsets, 4, 0, 700)
         assert rc == api.E_ARG and (v, m) == (0, 0) and "newline" in api.lib().trre_last_error().decode()
-        assert bool((out == BFILL).all()) and bool((oo == FILL).all()) and bool((valid == FILL).all())
+        for t in (out, oo, valid):
+            assert_untouched(t, at)
     # ... and the same strings go through: [12 x 50], [], [12 x 250], [ab]: every digit is inside a match
     rc, v, m, out, oo, valid = raw(p, values, len(data), offsets, 4, 0, 700)
     assert (rc, v, m) == (0, 4, 2) and lst(oo[:5]) == [0, 0, 0, 0, 2] and blob(out[:2]) == b"ab" and lst(valid[:1]) == [15]
@@ -295,17 +249,10 @@ def test_interleaved_with_the_other_span_calls_on_one_program():
     """field_strings, filter_strings, split_strings, span_strings and field_strings again, back to back on ONE program: a small
     input, a 330 KiB one, none, an input of exactly one tile and of one tile and a byte, the large one again.  The buffers the
     calls share only grow and every pass carves them anew: every result stays right"""
-    rng = random.Random(195)
-    word = lambda k: bytes(rng.choice(b"ab12 ,") for _ in range(k))
-    large, total = [], 0
-    while total < 330 * 1024:
-        large.append(word(rng.choice((0, 0, 1, 2, 5, 17, 40, 100, 300, 2000))))
-        total += len(large[-1])
-    tile = [word(1024) for _ in range(16)]
-    more = tile[:15] + [word(1025)]
-    assert sum(map(len, tile)) == 16384 and sum(map(len, more)) == 16385
+    seq = sequence(195, b"a1b", lambda rng, k: bytes(rng.choice(b"ab12 ,") for _ in range(k)), framed=False)
     p, spanner = trre_amd.Program("[0-9]+", "nft", "spans"), Spanner("[0-9]+")
-    for label, recs in (("tiny", [b"a1b"]), ("large", large), ("none", []), ("one tile", tile), ("one tile and a byte", more), ("large again", large)):
+    for label in ("tiny", "large", "none", "one tile", "one tile and a byte", "large again"):
+        recs = seq[label]
         spans = spanner.lines(recs)
         data, off = pack(recs)
         values, offsets = to_dev(data), off_dev(off)

@@ -12,52 +12,20 @@ import filter_lib
 import span_lib
 import split_lib
 import trre_amd
-from span_lib import LAYOUTS, PAIRS, Spanner, pack
+from gpu_column_lib import BFILL, FILL, PAD, assert_prefix, assert_untouched, blob, carve, dev, lst, off_dev, pack, sequence, soup, to_dev, words
+from span_lib import LAYOUTS, PAIRS, Spanner
 from trre_amd import api
 
 pytestmark = pytest.mark.gpu
 
-FILL = -7
-BFILL = 0xA5
-PAD = 8
 POOL = [b"", b"cat", b"a cat and a dog", b"xyz", b"\0 cat", b"do\0g cat", b"catdogcat", b"c" * 40]
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data, mis=0):
-    """the bytes on the device, at an address that is `mis` past a 16-byte boundary"""
-    import torch
-    t = torch.zeros(len(data) + 32, dtype=torch.uint8, device=dev())
-    at = (-t.data_ptr()) % 16 + mis
-    v = t[at:at + len(data)]
-    if data:
-        v.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
-    assert len(data) == 0 or v.data_ptr() % 16 == mis % 16
-    return v
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
-def words(n):
-    import torch
-    return torch.full((n,), FILL, dtype=torch.int64, device=dev())
 
 
 def raw(p, values, n, offsets, nrec, cap, rcap, invert=False, null=False, out=None, ooff=None, rows=None, out_mis=0):
     """the C ABI itself, with sentinel-filled arrays: (rc, *n_kept, *out_len, d_out, d_out_off, d_rows); d_out lies `out_mis` past
     a 16-byte boundary"""
-    import torch
     if out is None:
-        t = torch.full((cap + PAD + 32,), BFILL, dtype=torch.uint8, device=dev())
-        at = (-t.data_ptr()) % 16 + out_mis
-        out = t[at:at + cap + PAD]
+        out = carve(cap, out_mis)
     if ooff is None:
         ooff = words(rcap + 1 + PAD)
     if rows is None:
@@ -67,14 +35,6 @@ def raw(p, values, n, offsets, nrec, cap, rcap, invert=False, null=False, out=No
                                               None if null else out.data_ptr(), cap, None if null else ooff.data_ptr(),
                                               None if null else rows.data_ptr(), rcap, ctypes.byref(k), ctypes.byref(m), None)
     return rc, k.value, m.value, out, ooff, rows
-
-
-def blob(t):
-    return t.cpu().numpy().tobytes()
-
-
-def lst(t):
-    return t.cpu().numpy().tolist()
 
 
 def check(p, spans, recs, label, mis=0, out_mis=0):
@@ -97,15 +57,10 @@ def check(p, spans, recs, label, mis=0, out_mis=0):
         assert blob(out) == want[0], (label, invert)
         rc, k, m, out2, oo2, rows2 = raw(p, values, len(data), offsets, nrec, need, kept, invert=invert, out_mis=out_mis)
         assert (rc, k, m) == (0, kept, need), (label, invert, rc, k, m, api.lib().trre_last_error())
-        assert blob(out2[:need]) == want[0] and bool((out2[need:] == BFILL).all()), (label, invert)
-        assert lst(oo2[:kept + 1]) == want[1] and bool((oo2[kept + 1:] == FILL).all()), (label, invert)
-        assert lst(rows2[:kept]) == want[2] and bool((rows2[kept:] == FILL).all()), (label, invert)
+        for t, w in zip((out2, oo2, rows2), want):
+            assert_prefix(t, w, (label, invert))
     assert sorted(wants[0][2] + wants[1][2]) == list(range(nrec)), label
     return wants[0]
-
-
-def soup(rng, alphabet, n, longest=30):
-    return [bytes(rng.choice(alphabet) for _ in range(rng.randrange(0, longest))) for _ in range(n)]
 
 
 def test_golden_and_paired_patterns():
@@ -210,7 +165,8 @@ def test_capacity_and_sizes():
 
         def refused(rc, k, m, out, oo, rows):
             assert (rc, k, m) == (api.E_CAPACITY, kept, need), (invert, rc, k, m)
-            assert bool((out == BFILL).all()) and bool((oo == FILL).all()) and bool((rows == FILL).all()), invert
+            for t in (out, oo, rows):
+                assert_untouched(t, invert)
 
         refused(*raw(p, values, len(data), offsets, nrec, 0, 0, invert=invert, null=True))
         refused(*raw(p, values, len(data), offsets, nrec, need - 1, kept, invert=invert))
@@ -218,9 +174,8 @@ def test_capacity_and_sizes():
         refused(*raw(p, values, len(data), offsets, nrec, need + 100, 0, invert=invert))
         rc, k, m, out, oo, rows = raw(p, values, len(data), offsets, nrec, need, kept, invert=invert)
         assert (rc, k, m) == (0, kept, need), (invert, rc, k, m)
-        assert blob(out[:need]) == want[0] and bool((out[need:] == BFILL).all()), invert
-        assert lst(oo[:kept + 1]) == want[1] and bool((oo[kept + 1:] == FILL).all()), invert
-        assert lst(rows[:kept]) == want[2] and bool((rows[kept:] == FILL).all()), invert
+        for t, w in zip((out, oo, rows), want):
+            assert_prefix(t, w, invert)
 
 
 def test_errors_touch_nothing():
@@ -232,8 +187,9 @@ def test_errors_touch_nothing():
     def untouched(rc_want, p, vals=values, offs=offsets, cap=700, rcap=64, **kw):
         rc, k, m, out, oo, rows = raw(p, vals, len(data), offs, 4, cap, rcap, **kw)
         assert rc == rc_want and (k, m) == (0, 0), (rc, k, m, api.lib().trre_last_error())
-        for name, t, fill in (("out", out, BFILL), ("ooff", oo, FILL), ("rows", rows, FILL)):
-            assert name in kw or bool((t == fill).all()), name
+        for name, t in (("out", out), ("ooff", oo), ("rows", rows)):
+            if name not in kw:
+                assert_untouched(t, name)
         assert lst(offsets) == off and blob(values) == data
 
     for mode in ("scan", "match", "find"):
@@ -266,7 +222,8 @@ def test_errors_touch_nothing():
         holed[at] = 10
         rc, k, m, out, oo, rows = raw(p, to_dev(bytes(holed)), len(data), offsets, 4, 700, 64)
         assert rc == api.E_ARG and (k, m) == (0, 0) and "newline" in api.lib().trre_last_error().decode()
-        assert bool((out == BFILL).all()) and bool((oo == FILL).all()) and bool((rows == FILL).all())
+        for t in (out, oo, rows):
+            assert_untouched(t, at)
     # ... and the same strings go through: [12 x 50], [], [12 x 250], [ab]
     rc, k, m, out, oo, rows = raw(p, values, len(data), offsets, 4, 700, 64)
     assert (rc, k, m) == (0, 2, 600) and lst(oo[:3]) == [0, 100, 600] and lst(rows[:2]) == [0, 2]
@@ -280,17 +237,10 @@ def test_interleaved_with_the_span_and_split_calls_on_one_program():
     """span_strings, filter_strings, split_strings, filter_strings(invert=True), count_strings back to back on ONE program: a
     330 KiB input, a tiny one, none, an input of exactly one tile and of one tile and a byte, the large one again.  The buffers the
     calls share only grow and every pass carves them anew: every result stays right"""
-    rng = random.Random(95)
-    word = lambda k: bytes(rng.choice(b"ab12 ,") for _ in range(k))
-    large, total = [], 0
-    while total < 330 * 1024:
-        large.append(word(rng.choice((0, 0, 1, 2, 5, 17, 40, 100, 300, 2000))))
-        total += len(large[-1])
-    tile = [word(1024) for _ in range(16)]
-    more = tile[:15] + [word(1025)]
-    assert sum(map(len, tile)) == 16384 and sum(map(len, more)) == 16385
+    seq = sequence(95, b"a1b", lambda rng, k: bytes(rng.choice(b"ab12 ,") for _ in range(k)), framed=False)
     p, spanner = trre_amd.Program("[0-9]+", "nft", "spans"), Spanner("[0-9]+")
-    for label, recs in (("large", large), ("tiny", [b"a1b"]), ("none", []), ("one tile", tile), ("one tile and a byte", more), ("large again", large)):
+    for label in ("large", "tiny", "none", "one tile", "one tile and a byte", "large again"):
+        recs = seq[label]
         spans = spanner.lines(recs)
         data, off = pack(recs)
         values, offsets = to_dev(data), off_dev(off)

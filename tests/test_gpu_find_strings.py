@@ -11,37 +11,13 @@ import pytest
 import find_lib
 import trre_amd
 from find_lib import EXTRA, Finder, lines_of
+from gpu_column_lib import BFILL as SENTINEL
+from gpu_column_lib import FILL, PAD, assert_prefix, assert_untouched, blob, dev, lst, off_dev, pack, to_dev
+from gpu_column_lib import words as filled      # (words() here makes strings of words)
 from oracle_lib import OracleError
 from trre_amd import api
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
-FILL = -7
-PAD = 8
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data):
-    import torch
-    return torch.frombuffer(bytearray(data or b"\0"), dtype=torch.uint8)[:len(data)].to(dev())
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
-def pack(recs):
-    off = [0]
-    for r in recs:
-        off.append(off[-1] + len(r))
-    return b"".join(recs), off
-
 
 def expect(finder, recs):
     """the specification: (bytes, match offsets, list offsets)"""
@@ -54,10 +30,9 @@ def expect(finder, recs):
 
 def raw(p, values, n, offsets, nrec, out_ptr, cap, match_cap, moff=None, null_moff=False):
     """the C ABI itself, with sentinel-filled offset arrays: (rc, *out_len, *n_matches, d_match_off, d_list_off)"""
-    import torch
     if moff is None:
-        moff = torch.full((match_cap + 1 + PAD,), FILL, dtype=torch.int64, device=dev())
-    loff = torch.full((nrec + 1 + PAD,), FILL, dtype=torch.int64, device=dev())
+        moff = filled(match_cap + 1 + PAD)
+    loff = filled(nrec + 1 + PAD)
     m, k = ctypes.c_size_t(77), ctypes.c_size_t(77)
     rc = api.lib().trre_find_device_strings(p._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, out_ptr, cap,
                                             None if null_moff else moff.data_ptr(), match_cap, loff.data_ptr(), ctypes.byref(k), ctypes.byref(m), None)
@@ -72,16 +47,16 @@ def check(p, finder, recs, label, out_mis=0):
     data, off = pack(recs)
     values, offsets = to_dev(data), off_dev(off)
     out, mo, lo = p.find_strings(values, offsets)
-    assert out.cpu().numpy().tobytes() == want[0], label
-    assert mo.cpu().numpy().tolist() == want[1], label
-    assert lo.cpu().numpy().tolist() == want[2], label
+    assert blob(out) == want[0], label
+    assert lst(mo) == want[1], label
+    assert lst(lo) == want[2], label
     big = torch.full((out_mis + need + 64,), SENTINEL, dtype=torch.uint8, device=dev())
     rc, m, k, mo2, lo2 = raw(p, values, len(data), offsets, nrec, big.data_ptr() + out_mis, need, found)
     assert (rc, m, k) == (0, need, found), (label, rc, m, k, api.lib().trre_last_error())
     assert big[out_mis:out_mis + m].cpu().numpy().tobytes() == want[0], label
     assert bool((big[:out_mis] == SENTINEL).all()) and bool((big[out_mis + m:] == SENTINEL).all()), label
-    assert mo2[:found + 1].cpu().numpy().tolist() == want[1] and bool((mo2[found + 1:] == FILL).all()), label
-    assert lo2[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo2[nrec + 1:] == FILL).all()), label
+    assert_prefix(mo2, want[1], label)
+    assert_prefix(lo2, want[2], label)
     return want
 
 
@@ -201,7 +176,7 @@ def test_in_place():
         v = t[base:base + len(data)]
         rc, m, k, mo, lo = raw(p, v, len(data), offsets, nrec, v.data_ptr(), need - 1, found)
         assert (rc, m, k) == (api.E_CAPACITY, need, found)
-        assert v.cpu().numpy().tobytes() == data and bool((mo == FILL).all())
+        assert blob(v) == data and bool((mo == FILL).all())
         assert lo[:nrec + 1].cpu().numpy().tolist() == want[2]
         rc, m, k, mo, lo = raw(p, v, len(data), offsets, nrec, v.data_ptr(), len(data), found)
         assert (rc, m, k) == (0, need, found)
@@ -226,17 +201,18 @@ def test_capacity_protocol():
         values, offsets = to_dev(data), off_dev(off)
         rc, m, k, _, lo = raw(p, values, len(data), offsets, nrec, None, 0, 0, null_moff=True)
         assert (rc, m, k) == (api.E_CAPACITY, need, found), (pat, rc, m, k)
-        assert lo[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo[nrec + 1:] == FILL).all()), pat
+        assert_prefix(lo, want[2], pat)
         out = torch.full((need + 64,), SENTINEL, dtype=torch.uint8, device=dev())
         for cap, mcap in ((need - 1, found), (need, found - 1)):
             rc, m, k, mo, lo = raw(p, values, len(data), offsets, nrec, out.data_ptr(), cap, mcap)
             assert (rc, m, k) == (api.E_CAPACITY, need, found), (pat, cap, mcap, rc, m, k)
-            assert bool((out == SENTINEL).all()) and bool((mo == FILL).all()), (pat, cap, mcap)
+            assert_untouched(out, (pat, cap, mcap))
+            assert_untouched(mo, (pat, cap, mcap))
             assert lo[:nrec + 1].cpu().numpy().tolist() == want[2], pat
         rc, m, k, mo, lo = raw(p, values, len(data), offsets, nrec, out.data_ptr(), need, found)
         assert (rc, m, k) == (0, need, found), (pat, rc, m, k)
-        assert out[:need].cpu().numpy().tobytes() == want[0] and bool((out[need:] == SENTINEL).all()), pat
-        assert mo[:found + 1].cpu().numpy().tolist() == want[1] and bool((mo[found + 1:] == FILL).all()), pat
+        assert_prefix(out, want[0], pat)
+        assert_prefix(mo, want[1], pat)
 
 
 def test_refusals_touch_nothing():
@@ -249,7 +225,9 @@ def test_refusals_touch_nothing():
     def untouched(rc_want, p, vals=values, offs=offsets, **kw):
         rc, m, k, mo, lo = raw(p, vals, len(data), offs, 4, out.data_ptr(), out.numel(), 64, **kw)
         assert rc == rc_want and m == 0 and k == 0, (rc, m, k, api.lib().trre_last_error())
-        assert bool((out == SENTINEL).all()) and bool((lo == FILL).all()) and ("moff" in kw or bool((mo == FILL).all()))
+        for name, t in (("out", out), ("loff", lo), ("moff", mo)):
+            if name not in kw:
+                assert_untouched(t, name)
 
     untouched(api.E_ARG, trre_amd.Program("[0-9]+:N", "nft"))                                    # a scan-mode program
     untouched(api.E_ARG, trre_amd.Program("[0-9]+:N", "nft", "match"))

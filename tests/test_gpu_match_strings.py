@@ -12,6 +12,7 @@ import pytest
 
 import golden_lib
 import trre_amd
+from gpu_column_lib import dev, off_dev, pack, to_dev
 from oracle_lib import Oracle, OracleError
 from trre_amd import api
 
@@ -23,28 +24,6 @@ SENTINEL = 0xA5
 THREADS = 16
 WIDE = "[a-h]{8}(a|b)[a-z ]*"                              # this build: 772 backward states, 16-bit symbols
 EXTRA = [".*(cat:dog).*(a|b){4}", "(a|b)*a(a|b){5}", WIDE]  # ... 19 (a byte per symbol), 16 (the last nibble-packed size)
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data):
-    import torch
-    return torch.frombuffer(bytearray(data or b"\0"), dtype=torch.uint8)[:len(data)].to(dev())
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
-def pack(recs):
-    off = [0]
-    for r in recs:
-        off.append(off[-1] + len(r))
-    return b"".join(recs), off
 
 
 class Memo:

@@ -12,46 +12,20 @@ import find_lib
 import span_lib
 import trre_amd
 from find_lib import Finder, lines_of
-from span_lib import LAYOUTS, PAIRS, Spanner, Weak, pack
+from gpu_column_lib import FILL, PAD, assert_prefix, assert_untouched, blob, dev, lst, off_dev, pack, soup, to_dev, words
+from span_lib import LAYOUTS, PAIRS, Spanner, Weak
 from trre_amd import api
 
 pytestmark = pytest.mark.gpu
 
-FILL = -7
-PAD = 8
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data, mis=0):
-    """the bytes on the device, at an address that is `mis` past a 16-byte boundary"""
-    import torch
-    t = torch.zeros(len(data) + 32, dtype=torch.uint8, device=dev())
-    at = (-t.data_ptr()) % 16 + mis
-    v = t[at:at + len(data)]
-    if data:
-        v.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
-    assert len(data) == 0 or v.data_ptr() % 16 == mis % 16
-    return v
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
 def raw(p, values, n, offsets, nrec, span_cap, null_spans=False, starts=None, ends=None, loff=None):
     """the C ABI itself, with sentinel-filled arrays: (rc, *n_matches, d_start, d_end, d_list_off)"""
-    import torch
     if starts is None:
-        starts = torch.full((span_cap + PAD,), FILL, dtype=torch.int64, device=dev())
+        starts = words(span_cap + PAD)
     if ends is None:
-        ends = torch.full((span_cap + PAD,), FILL, dtype=torch.int64, device=dev())
+        ends = words(span_cap + PAD)
     if loff is None:
-        loff = torch.full((nrec + 1 + PAD,), FILL, dtype=torch.int64, device=dev())
+        loff = words(nrec + 1 + PAD)
     k = ctypes.c_size_t(77)
     rc = api.lib().trre_span_device_strings(p._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec,
                                             None if null_spans else starts.data_ptr(), None if null_spans else ends.data_ptr(), span_cap,
@@ -66,19 +40,14 @@ def check(p, per, recs, label, mis=0):
     found, nrec = len(want[0]), len(recs)
     values, offsets = to_dev(data, mis), off_dev(off)
     st, en, lo = p.span_strings(values, offsets)
-    assert st.cpu().numpy().tolist() == want[0], label
-    assert en.cpu().numpy().tolist() == want[1], label
-    assert lo.cpu().numpy().tolist() == want[2], label
+    assert lst(st) == want[0], label
+    assert lst(en) == want[1], label
+    assert lst(lo) == want[2], label
     rc, k, st2, en2, lo2 = raw(p, values, len(data), offsets, nrec, found)
     assert (rc, k) == (0, found), (label, rc, k, api.lib().trre_last_error())
-    assert st2[:found].cpu().numpy().tolist() == want[0] and bool((st2[found:] == FILL).all()), label
-    assert en2[:found].cpu().numpy().tolist() == want[1] and bool((en2[found:] == FILL).all()), label
-    assert lo2[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo2[nrec + 1:] == FILL).all()), label
+    for t, w in zip((st2, en2, lo2), want):
+        assert_prefix(t, w, label)
     return want
-
-
-def soup(rng, alphabet, n, longest=30):
-    return [bytes(rng.choice(alphabet) for _ in range(rng.randrange(0, longest))) for _ in range(n)]
 
 
 def test_golden_and_paired_patterns():
@@ -123,13 +92,13 @@ def test_counts_and_gaps_on_every_usable_golden_vector():
             refused += 1
             continue
         p, finder, weak = progs[pat]
-        blob, off = pack(recs)
-        values, offsets = to_dev(blob), off_dev(off)
+        text, off = pack(recs)
+        values, offsets = to_dev(text), off_dev(off)
         st, en, lo = p.span_strings(values, offsets)
-        got = span_lib.relative(st.cpu().numpy().tolist(), en.cpu().numpy().tolist(), lo.cpu().numpy().tolist(), off)
+        got = span_lib.relative(lst(st), lst(en), lst(lo), off)
         counts = [len(w) for w in finder.lines(recs)]
         assert [len(w) for w in got] == counts, (pat, name)
-        assert p.count_strings(values, offsets).cpu().numpy().tolist() == counts, (pat, name)
+        assert lst(p.count_strings(values, offsets)) == counts, (pat, name)
         for l, sp, (k, rest) in zip(recs, got, weak.lines(recs)):
             assert len(sp) == k and span_lib.gaps(l, sp) == rest, (pat, name, l)
             assert all(0 <= s <= e <= len(l) for s, e in sp), (pat, name, l, sp)
@@ -138,8 +107,8 @@ def test_counts_and_gaps_on_every_usable_golden_vector():
     assert len(dead) == 13
     for pat, name, data in dead:
         recs = lines_of(data)
-        blob, off = pack(recs)
-        rc, k, _, _, _ = raw(trre_amd.Program(pat, "nft", "spans"), to_dev(blob), len(blob), off_dev(off), len(recs), 1 << 16)
+        text, off = pack(recs)
+        rc, k, _, _, _ = raw(trre_amd.Program(pat, "nft", "spans"), to_dev(text), len(text), off_dev(off), len(recs), 1 << 16)
         assert rc == api.E_DIVERGES and k == 0, (pat, name, rc, k)
         assert "stack max capacity" in api.lib().trre_last_error().decode(), (pat, name)
 
@@ -202,16 +171,17 @@ def test_capacity_and_sizes():
         values, offsets = to_dev(data), off_dev(off)
         rc, k, _, _, lo = raw(p, values, len(data), offsets, nrec, 0, null_spans=True)
         assert (rc, k) == (api.E_CAPACITY, found), (prog, rc, k)
-        assert lo[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo[nrec + 1:] == FILL).all()), prog
+        assert_prefix(lo, want[2], prog)
         rc, k, st, en, lo = raw(p, values, len(data), offsets, nrec, found - 1)
         assert (rc, k) == (api.E_CAPACITY, found), (prog, rc, k)
-        assert bool((st == FILL).all()) and bool((en == FILL).all()), prog
-        assert lo[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo[nrec + 1:] == FILL).all()), prog
-        assert p.count_strings(values, offsets).cpu().numpy().tolist() == [len(w) for w in per], prog
+        assert_untouched(st, prog)
+        assert_untouched(en, prog)
+        assert_prefix(lo, want[2], prog)
+        assert lst(p.count_strings(values, offsets)) == [len(w) for w in per], prog
         rc, k, st, en, lo = raw(p, values, len(data), offsets, nrec, found)
         assert (rc, k) == (0, found), (prog, rc, k)
-        assert st[:found].cpu().numpy().tolist() == want[0] and en[:found].cpu().numpy().tolist() == want[1], prog
-        assert bool((st[found:] == FILL).all()) and bool((en[found:] == FILL).all()), prog
+        assert_prefix(st, want[0], prog)
+        assert_prefix(en, want[1], prog)
     # no match at all: the size query itself succeeds
     p = trre_amd.Program("[0-9]+", "nft", "spans")
     values, offsets = to_dev(b"abcdef"), off_dev([0, 2, 2, 6])
@@ -229,7 +199,8 @@ def test_errors_touch_nothing():
         rc, k, st, en, lo = raw(p, vals, len(data), offs, 4, 64, **kw)
         assert rc == rc_want and k == 0, (rc, k, api.lib().trre_last_error())
         for name, t in (("starts", st), ("ends", en), ("loff", lo)):
-            assert name in kw or bool((t == FILL).all()), name
+            if name not in kw:
+                assert_untouched(t, name)
 
     for mode in ("scan", "match", "find"):
         untouched(api.E_ARG, trre_amd.Program("[0-9]+:N", "nft", mode))                          # wrong-mode programs
@@ -242,13 +213,13 @@ def test_errors_touch_nothing():
     assert e.value.code == api.E_UNSUPPORTED
     for bad in ([1, 100, 100, 600, 602], [0, 100, 90, 600, 602], [0, 100, 100, 600, 601], [0, 100, 100, 603, 602]):
         untouched(api.E_ARG, p, offs=off_dev(bad))                                               # bad offsets: nothing written
-    shared = torch.full((64 + PAD,), FILL, dtype=torch.int64, device=dev())
+    shared = words(64 + PAD)
     untouched(api.E_ARG, p, starts=shared, ends=shared[8:])                                      # the span arrays overlap
-    assert bool((shared == FILL).all())
+    assert_untouched(shared)
     untouched(api.E_ARG, p, starts=offsets)                                                      # d_start on the offsets
     untouched(api.E_ARG, p, loff=offsets)                                                        # d_list_off on the offsets
     untouched(api.E_ARG, p, ends=values[:520].view(torch.int64))                                 # d_end inside d_in
-    assert offsets.cpu().tolist() == off and values.cpu().numpy().tobytes() == data
+    assert offsets.cpu().tolist() == off and blob(values) == data
     # a string with an inner '\n': at the start, in the middle, as the last byte of the buffer
     for at in (0, 300, len(data) - 1):
         holed = bytearray(data)

@@ -13,52 +13,20 @@ import span_lib
 import split_lib
 import trre_amd
 from find_lib import Finder, lines_of
-from span_lib import LAYOUTS, PAIRS, Spanner, Weak, pack
+from gpu_column_lib import BFILL, FILL, PAD, assert_prefix, assert_untouched, blob, carve, dev, lst, off_dev, pack, sequence, soup, to_dev, words
+from span_lib import LAYOUTS, PAIRS, Spanner, Weak
 from split_lib import cut_pieces, split_lines
 from trre_amd import api
 
 pytestmark = pytest.mark.gpu
 
-FILL = -7
-BFILL = 0xA5
-PAD = 8
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data, mis=0):
-    """the bytes on the device, at an address that is `mis` past a 16-byte boundary"""
-    import torch
-    t = torch.zeros(len(data) + 32, dtype=torch.uint8, device=dev())
-    at = (-t.data_ptr()) % 16 + mis
-    v = t[at:at + len(data)]
-    if data:
-        v.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
-    assert len(data) == 0 or v.data_ptr() % 16 == mis % 16
-    return v
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
-def words(n):
-    import torch
-    return torch.full((n,), FILL, dtype=torch.int64, device=dev())
 
 
 def raw(p, values, n, offsets, nrec, cap, pcap, null=False, out=None, poff=None, loff=None, out_mis=0):
     """the C ABI itself, with sentinel-filled arrays: (rc, *n_pieces, *out_len, d_out, d_piece_off, d_list_off); d_out lies
     `out_mis` past a 16-byte boundary"""
-    import torch
     if out is None:
-        t = torch.full((cap + PAD + 32,), BFILL, dtype=torch.uint8, device=dev())
-        at = (-t.data_ptr()) % 16 + out_mis
-        out = t[at:at + cap + PAD]
+        out = carve(cap, out_mis)
     if poff is None:
         poff = words(pcap + 1 + PAD)
     if loff is None:
@@ -69,10 +37,6 @@ def raw(p, values, n, offsets, nrec, cap, pcap, null=False, out=None, poff=None,
     return rc, k.value, m.value, out, poff, loff
 
 
-def blob(t):
-    return t.cpu().numpy().tobytes()
-
-
 def check(p, per, recs, label, mis=0, out_mis=0):
     """one call through Program.split_strings and one through the C ABI with exact room, against the per-string pieces `per`"""
     data, off = pack(recs)
@@ -81,19 +45,14 @@ def check(p, per, recs, label, mis=0, out_mis=0):
     assert pieces == want[2][-1] and sum(map(len, recs)) >= need
     values, offsets = to_dev(data, mis), off_dev(off)
     out, po, lo = p.split_strings(values, offsets)
-    assert lo.cpu().numpy().tolist() == want[2], label
-    assert po.cpu().numpy().tolist() == want[1], label
+    assert lst(lo) == want[2], label
+    assert lst(po) == want[1], label
     assert blob(out) == want[0], label
     rc, k, m, out2, po2, lo2 = raw(p, values, len(data), offsets, nrec, need, pieces, out_mis=out_mis)
     assert (rc, k, m) == (0, pieces, need), (label, rc, k, m, api.lib().trre_last_error())
-    assert blob(out2[:need]) == want[0] and bool((out2[need:] == BFILL).all()), label
-    assert po2[:pieces + 1].cpu().numpy().tolist() == want[1] and bool((po2[pieces + 1:] == FILL).all()), label
-    assert lo2[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo2[nrec + 1:] == FILL).all()), label
+    for t, w in zip((out2, po2, lo2), want):
+        assert_prefix(t, w, label)
     return want
-
-
-def soup(rng, alphabet, n, longest=30):
-    return [bytes(rng.choice(alphabet) for _ in range(rng.randrange(0, longest))) for _ in range(n)]
 
 
 def test_golden_and_paired_patterns():
@@ -139,8 +98,8 @@ def test_counts_and_joined_pieces_on_every_usable_golden_vector():
         p, finder, weak = progs[pat]
         data2, off = pack(recs)
         out, po, lo = p.split_strings(to_dev(data2), off_dev(off))
-        got = split_lib.per_string(blob(out), po.cpu().numpy().tolist(), lo.cpu().numpy().tolist())
-        assert len(got) == len(recs) and po.cpu().numpy().tolist()[-1] == out.numel(), (pat, name)
+        got = split_lib.per_string(blob(out), lst(po), lst(lo))
+        assert len(got) == len(recs) and lst(po)[-1] == out.numel(), (pat, name)
         counts = [len(w) for w in finder.lines(recs)]
         assert [len(w) - 1 for w in got] == counts, (pat, name)
         for l, pieces, (k, rest) in zip(recs, got, weak.lines(recs)):
@@ -226,8 +185,9 @@ def test_capacity_and_sizes():
 
         def refused(rc, k, m, out, po, lo):
             assert (rc, k, m) == (api.E_CAPACITY, pieces, need), (prog, rc, k, m)
-            assert bool((out == BFILL).all()) and bool((po == FILL).all()), prog
-            assert lo[:nrec + 1].cpu().numpy().tolist() == want[2] and bool((lo[nrec + 1:] == FILL).all()), prog
+            assert_untouched(out, prog)
+            assert_untouched(po, prog)
+            assert_prefix(lo, want[2], prog)
 
         refused(*raw(p, values, len(data), offsets, nrec, 0, 0, null=True))
         refused(*raw(p, values, len(data), offsets, nrec, need - 1, pieces))
@@ -235,8 +195,8 @@ def test_capacity_and_sizes():
         refused(*raw(p, values, len(data), offsets, nrec, need + 100, 0))
         rc, k, m, out, po, lo = raw(p, values, len(data), offsets, nrec, need, pieces)
         assert (rc, k, m) == (0, pieces, need), (prog, rc, k, m)
-        assert blob(out[:need]) == want[0] and bool((out[need:] == BFILL).all()), prog
-        assert po[:pieces + 1].cpu().numpy().tolist() == want[1] and bool((po[pieces + 1:] == FILL).all()), prog
+        assert_prefix(out, want[0], prog)
+        assert_prefix(po, want[1], prog)
     # nothing kept at all: d_out may be null with cap 0 while the piece offsets are filled
     p = trre_amd.Program("[0-9]+", "nft", "spans")
     values, offsets = to_dev(b"123456"), off_dev([0, 2, 2, 6])
@@ -258,8 +218,9 @@ def test_errors_touch_nothing():
     def untouched(rc_want, p, vals=values, offs=offsets, cap=700, pcap=64, **kw):
         rc, k, m, out, po, lo = raw(p, vals, len(data), offs, 4, cap, pcap, **kw)
         assert rc == rc_want and (k, m) == (0, 0), (rc, k, m, api.lib().trre_last_error())
-        for name, t, fill in (("out", out, BFILL), ("poff", po, FILL), ("loff", lo, FILL)):
-            assert name in kw or bool((t == fill).all()), name
+        for name, t in (("out", out), ("poff", po), ("loff", lo)):
+            if name not in kw:
+                assert_untouched(t, name)
         assert offsets.cpu().tolist() == off and blob(values) == data
 
     for mode in ("scan", "match", "find"):
@@ -291,7 +252,8 @@ def test_errors_touch_nothing():
         holed[at] = 10
         rc, k, m, out, po, lo = raw(p, to_dev(bytes(holed)), len(data), offsets, 4, 700, 64)
         assert rc == api.E_ARG and (k, m) == (0, 0) and "newline" in api.lib().trre_last_error().decode()
-        assert bool((out == BFILL).all()) and bool((po == FILL).all()) and bool((lo == FILL).all())
+        for t in (out, po, lo):
+            assert_untouched(t, at)
     # ... and the same strings go through
     rc, k, m, out, po, lo = raw(p, values, len(data), offsets, 4, 700, 64)
     assert (rc, k, m) == (0, 6, 2) and lo[:5].cpu().tolist() == [0, 2, 3, 5, 6] and po[:7].cpu().tolist() == [0, 0, 0, 0, 0, 0, 2]
@@ -302,17 +264,10 @@ def test_interleaved_with_the_span_calls_on_one_program():
     """span_strings, split_strings, count_strings, split_strings back to back on ONE program: a large input, a tiny one, none,
     staged texts of exactly one framed-text tile and of one tile and a byte.  The buffers the calls share only grow and every
     pass carves them anew: every result stays right"""
-    rng = random.Random(84)
-    word = lambda k: bytes(rng.choice(b"ab12 ,") for _ in range(k))
-    large, total = [], 0
-    while total < 330 * 1024:
-        large.append(word(rng.choice((0, 0, 1, 2, 5, 17, 40, 100, 300, 2000))))
-        total += len(large[-1])
-    tile = [word(1023) for _ in range(16)]
-    more = tile[:15] + [word(1024)]
-    assert sum(map(len, tile)) + 16 == 16384
+    seq = sequence(84, b"a1b", lambda rng, k: bytes(rng.choice(b"ab12 ,") for _ in range(k)))
     p, spanner = trre_amd.Program("[0-9]+", "nft", "spans"), Spanner("[0-9]+")
-    for label, recs in (("large", large), ("tiny", [b"a1b"]), ("none", []), ("one tile", tile), ("one tile and a byte", more), ("large again", large)):
+    for label in ("large", "tiny", "none", "one tile", "one tile and a byte", "large again"):
+        recs = seq[label]
         spans = spanner.lines(recs)
         per = [cut_pieces(l, sp) for l, sp in zip(recs, spans)]
         data, off = pack(recs)
@@ -320,11 +275,11 @@ def test_interleaved_with_the_span_calls_on_one_program():
         want_spans, want = span_lib.expect(spans, off), split_lib.expect(per)
         for step in range(2):
             st, en, lo = p.span_strings(values, offsets)
-            assert (st.cpu().numpy().tolist(), en.cpu().numpy().tolist(), lo.cpu().numpy().tolist()) == want_spans, (label, step)
+            assert (lst(st), lst(en), lst(lo)) == want_spans, (label, step)
             out, po, lo = p.split_strings(values, offsets)
-            assert (blob(out), po.cpu().numpy().tolist(), lo.cpu().numpy().tolist()) == want, (label, step)
-            assert p.count_strings(values, offsets).cpu().numpy().tolist() == [len(w) for w in spans], (label, step)
+            assert (blob(out), lst(po), lst(lo)) == want, (label, step)
+            assert lst(p.count_strings(values, offsets)) == [len(w) for w in spans], (label, step)
             out, po, lo = p.split_strings(values, offsets)
-            assert (blob(out), po.cpu().numpy().tolist(), lo.cpu().numpy().tolist()) == want, (label, step)
+            assert (blob(out), lst(po), lst(lo)) == want, (label, step)
             # the kept bytes are the input minus the matched ones (checked here, not in the call)
             assert out.numel() == len(data) - sum(e - s for w in spans for s, e in w), (label, step)

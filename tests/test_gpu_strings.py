@@ -11,6 +11,7 @@ import pytest
 
 import golden_lib
 import trre_amd
+from gpu_column_lib import dev, off_dev, pack, to_dev
 from oracle_lib import Oracle, OracleError, scan_mt
 from trre_amd import api
 
@@ -20,28 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 SENTINEL = 0xA5
 THREADS = 16
-
-
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def to_dev(data):
-    import torch
-    return torch.frombuffer(bytearray(data or b"\0"), dtype=torch.uint8)[:len(data)].to(dev())
-
-
-def off_dev(off):
-    import torch
-    return torch.tensor(list(off), dtype=torch.int64, device=dev())
-
-
-def pack(recs):
-    off = [0]
-    for r in recs:
-        off.append(off[-1] + len(r))
-    return b"".join(recs), off
 
 
 def run(p, values, offsets):

@@ -14,7 +14,6 @@ of its own, no counters in it) and read the k_field_* rows.
 
     python tools/field_strings_bench.py [--gib 2] [--steps 5] [--warmup 1] [--forms line,4KiB] [--patterns ',' '[0-9]+']
 """
-import argparse
 import ctypes
 import json
 import os
@@ -26,43 +25,28 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
 
-import corpora  # noqa: E402
+import column_bench  # noqa: E402
 import trre_amd  # noqa: E402
-from records_bench import timed  # noqa: E402
+from column_bench import timed  # noqa: E402
 from trre_amd import api  # noqa: E402
 
 KS = (0, 1, -1)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gib", type=float, default=2.0)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--forms", default="line,4KiB")
+    ap = column_bench.parser()
     ap.add_argument("--patterns", nargs="+", default=[",", "[0-9]+"])
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = int(args.gib * (1 << 30))
     lib = api.lib()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    x = corpora.printable_lines(n, corpora.SEED0 + 7, dev)
-    step = 1 << 30                                   # (nonzero over the whole buffer at once is beyond torch's index range)
-    ends = torch.cat([(x[lo:lo + step] == 10).nonzero().flatten() + (lo + 1) for lo in range(0, n, step)])
-    stripped = torch.cat([x[lo:lo + step][x[lo:lo + step] != 10] for lo in range(0, n, step)])
-    zero = torch.zeros(1, dtype=torch.int64, device=dev)
-    s_off = torch.cat([zero, ends - torch.arange(1, ends.numel() + 1, dtype=torch.int64, device=dev)])
-    del ends, x
+    stripped, s_off = column_bench.line_column(n, dev)[1:]
     m, k = ctypes.c_size_t(), ctypes.c_size_t()
     for pattern in args.patterns:
         p = trre_amd.Program(pattern, "nft", "spans")
         for label in args.forms.split(","):
-            if label == "line":
-                values, offs = stripped, s_off
-            else:
-                rows = stripped.numel() // 4096
-                values = stripped[:rows * 4096]
-                offs = torch.arange(0, rows * 4096 + 1, 4096, dtype=torch.int64, device=dev)
+            values, offs = column_bench.form(label, stripped, s_off)
             nrec, nb = offs.numel() - 1, values.numel()
             lo = torch.empty_like(offs)
             bits = torch.zeros((nrec + 63) // 64, dtype=torch.int64, device=dev)

@@ -10,7 +10,6 @@ k_match_* rows next to k_str_stage's.
 
     python tools/match_strings_bench.py [--gib 8] [--steps 5] [--warmup 1] [--forms line,4KiB] [--pattern '[a:A-m:M].*']
 """
-import argparse
 import ctypes
 import json
 import os
@@ -22,44 +21,32 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
 
-import corpora  # noqa: E402
+import column_bench  # noqa: E402
 import trre_amd  # noqa: E402
-from records_bench import timed  # noqa: E402
+from column_bench import timed  # noqa: E402
 from trre_amd import api  # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gib", type=float, default=8.0)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--forms", default="line,4KiB")
+    ap = column_bench.parser(gib=8.0)
     ap.add_argument("--pattern", default="[a:A-m:M].*")      # accepts the lines that start with a..m: about a third of the printable ones
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = int(args.gib * (1 << 30))
     lib = api.lib()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    x = corpora.printable_lines(n, corpora.SEED0 + 7, dev)
-    step = 1 << 30                                   # (nonzero over the whole buffer at once is beyond torch's index range)
-    ends = torch.cat([(x[lo:lo + step] == 10).nonzero().flatten() + (lo + 1) for lo in range(0, n, step)])
-    stripped = torch.cat([x[lo:lo + step][x[lo:lo + step] != 10] for lo in range(0, n, step)])
-    zero = torch.zeros(1, dtype=torch.int64, device=dev)
-    s_off = torch.cat([zero, ends - torch.arange(1, ends.numel() + 1, dtype=torch.int64, device=dev)])
-    del ends
+    x, stripped, s_off = column_bench.line_column(n, dev)
     pm = trre_amd.Program(args.pattern, "nft", "match")
     ps = trre_amd.Program(args.pattern, "nft")
     ps.set_kernel(trre_amd.KERNEL_GUIDED_GEN)                # the family match mode runs on
     m, k = ctypes.c_size_t(), ctypes.c_size_t()
     for label in args.forms.split(","):
-        if label == "line":
-            joined, values, offs = x, stripped, s_off
-        else:
-            rows = stripped.numel() // 4096
-            values = stripped[:rows * 4096]
-            offs = torch.arange(0, rows * 4096 + 1, 4096, dtype=torch.int64, device=dev)
-            joined = torch.cat([values.view(rows, 4096), torch.full((rows, 1), 10, dtype=torch.uint8, device=dev)], dim=1).flatten()
+        values, offs = column_bench.form(label, stripped, s_off)
         nrec = offs.numel() - 1
+        if label == "line":
+            joined = x
+        else:
+            joined = torch.cat([values.view(nrec, 4096), torch.full((nrec, 1), 10, dtype=torch.uint8, device=dev)], dim=1).flatten()
         cap = joined.numel() + 64
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         oo = torch.empty_like(offs)

@@ -12,9 +12,7 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,20 +23,8 @@ import torch  # noqa: E402
 import corpora  # noqa: E402
 import dictgen  # noqa: E402
 import trre_amd  # noqa: E402
+from column_bench import timed  # noqa: E402
 from trre_amd import api  # noqa: E402
-
-
-def timed(fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(steps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ms)
 
 
 def main():

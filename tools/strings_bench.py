@@ -24,7 +24,7 @@ import torch  # noqa: E402
 import corpora  # noqa: E402
 import dictgen  # noqa: E402
 import trre_amd  # noqa: E402
-from records_bench import timed  # noqa: E402
+from column_bench import timed  # noqa: E402
 from trre_amd import api  # noqa: E402
 
 

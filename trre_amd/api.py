@@ -146,6 +146,63 @@ def _retry_capacity(call, out, m, device):
     return rc, out
 
 
+def _fetch(export, *args):
+    """the two-call blob fetch: export(*args, None, 0) says the size, export(*args, buf, size) fills it; the bytes, b"" for none"""
+    n = export(*args, None, 0)
+    buf = ctypes.create_string_buffer(max(n, 1))
+    export(*args, buf, n)
+    return buf.raw[:n]
+
+
+def _query_then_fill(call, query, alloc, sizes, device):
+    """the size query call(*query), null pointers and no room, leaves what to allocate in sizes (c_size_t's); alloc(*their values)
+    makes arrays of exactly that size and returns (result, the filling call's arguments); the filling call is made only when the
+    query said E_CAPACITY, and reports the same sizes: the result"""
+    import torch
+    with torch.cuda.device(device):
+        rc = call(*query)
+        if rc not in (0, E_CAPACITY):
+            _check(rc)
+        asked = [x.value for x in sizes]
+        result, fill = alloc(*asked)
+        if rc == E_CAPACITY:
+            _check(call(*fill))
+            assert [x.value for x in sizes] == asked
+    return result
+
+
+def _validity(words, nrec, packed):
+    """the validity bitmap the library wrote into words (int64): packed, its 8 * ceil(nrec / 64) bytes; else one torch.bool a string"""
+    import torch
+    bitmap = words.view(torch.uint8)[:8 * ((nrec + 63) // 64)]
+    if packed:
+        return bitmap
+    shifts = torch.arange(8, dtype=torch.uint8, device=words.device)
+    return ((bitmap.unsqueeze(1) >> shifts) & 1).to(torch.bool).flatten()[:nrec]
+
+
+def _default_outputs(out, out_offsets, n, nrec, device):
+    """out and out_offsets of the scan-like calls, made where the caller gave none"""
+    import torch
+    if out is None:
+        out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=device)
+    if out_offsets is None:
+        out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=device)
+    return out, out_offsets
+
+
+def _read_back(out, off, list_off=None):
+    """the host read-back of the *_list methods: item j is out[off[j]:off[j + 1]], a list of bytes; with list_off a list of such
+    lists, items list_off[i] .. list_off[i + 1] - 1 in list i"""
+    blob = out.cpu().numpy().tobytes()
+    o = off.cpu().numpy().tolist()
+    items = [blob[o[j]:o[j + 1]] for j in range(len(o) - 1)]
+    if list_off is None:
+        return items
+    lo = list_off.cpu().numpy().tolist()
+    return [items[lo[i]:lo[i + 1]] for i in range(len(lo) - 1)]
+
+
 def _pack(records, device):
     """a list of bytes as a column on the device: (recs, host offsets, values, offsets)"""
     import numpy as np
@@ -193,82 +250,45 @@ class Program:
         _check(lib().trre_set_kernel(self._h, family))
 
     def export_tables(self):
-        n = lib().trre_export_tables(self._h, None, 0)
-        buf = ctypes.create_string_buffer(n)
-        lib().trre_export_tables(self._h, buf, n)
-        return buf.raw
+        return _fetch(lib().trre_export_tables, self._h)
 
     def export_stream_tables(self):
-        n = lib().trre_export_stream_tables(self._h, None, 0)
-        buf = ctypes.create_string_buffer(max(n, 1))
-        lib().trre_export_stream_tables(self._h, buf, n)
-        return buf.raw[:n]
+        return _fetch(lib().trre_export_stream_tables, self._h)
+
+    def _guided(self, *which):
+        """the blobs `which` of trre_export_guided_tables, each b"" where the program has none"""
+        return tuple(_fetch(lib().trre_export_guided_tables, self._h, w) for w in which)
 
     def export_guided_tables(self):
         """(backward DFA blob, forward tables blob) of the guided families, or (b"", b"")"""
-        blobs = []
-        for which in (0, 1):
-            n = lib().trre_export_guided_tables(self._h, which, None, 0)
-            buf = ctypes.create_string_buffer(max(n, 1))
-            lib().trre_export_guided_tables(self._h, which, buf, n)
-            blobs.append(buf.raw[:n])
-        return tuple(blobs)
+        return self._guided(0, 1)
 
     def export_accept_table(self):
         """match mode, guided tables: one byte per backward state, 1 where a line whose first byte carries that symbol is
         accepted (the verdict table of match_strings), or b"" """
-        n = lib().trre_export_guided_tables(self._h, 4, None, 0)
-        buf = ctypes.create_string_buffer(max(n, 1))
-        lib().trre_export_guided_tables(self._h, 4, buf, n)
-        return buf.raw[:n]
+        return self._guided(4)[0]
 
     def export_find_tables(self):
         """find mode: (backward DFA blob, texts forward tables blob, marks forward tables blob), or (b"", b"", b"")"""
-        blobs = []
-        for which in (0, 5, 6):
-            n = lib().trre_export_guided_tables(self._h, which, None, 0)
-            buf = ctypes.create_string_buffer(max(n, 1))
-            lib().trre_export_guided_tables(self._h, which, buf, n)
-            blobs.append(buf.raw[:n])
-        if not blobs[1]:
-            return (b"", b"", b"")
-        return tuple(blobs)
+        blobs = self._guided(0, 5, 6)
+        return blobs if blobs[1] else (b"", b"", b"")
 
     def export_span_tables(self):
         """spans mode: (backward DFA blob, the markers' forward tables blob), or (b"", b"")"""
-        blobs = []
-        for which in (0, 7):
-            n = lib().trre_export_guided_tables(self._h, which, None, 0)
-            buf = ctypes.create_string_buffer(max(n, 1))
-            lib().trre_export_guided_tables(self._h, which, buf, n)
-            blobs.append(buf.raw[:n])
-        if not blobs[1]:
-            return (b"", b"")
-        return tuple(blobs)
+        blobs = self._guided(0, 7)
+        return blobs if blobs[1] else (b"", b"")
 
     def export_gen_tables(self):
         """generator modes: the tables of the device enumeration (gen_block.hpp), or b"" """
-        n = lib().trre_export_guided_tables(self._h, 2, None, 0)
-        buf = ctypes.create_string_buffer(max(n, 1))
-        lib().trre_export_guided_tables(self._h, 2, buf, n)
-        return buf.raw[:n]
+        return self._guided(2)[0]
 
     def export_guard_tables(self):
         """the stack guard's tables (guard_block.hpp), or b"" when the pattern cannot exhaust the reference's stack"""
-        n = lib().trre_export_guided_tables(self._h, 3, None, 0)
-        buf = ctypes.create_string_buffer(max(n, 1))
-        lib().trre_export_guided_tables(self._h, 3, buf, n)
-        return buf.raw[:n]
+        return self._guided(3)[0]
 
     def lazy_tables(self):
         """DFT engine (CPU test tier): the lazily determinised tables as they stand: (header, entries, pool)"""
-        parts = []
-        for which in (0, 1, 2):
-            n = lib().trre_debug_lazy_tables(self._h, which, None, 0)
-            buf = ctypes.create_string_buffer(max(n, 1))
-            lib().trre_debug_lazy_tables(self._h, which, buf, n)
-            parts.append(buf.raw[:n])
-        return tuple(parts)
+        return tuple(_fetch(lib().trre_debug_lazy_tables, self._h, which) for which in (0, 1, 2))
 
     def lazy_explore(self, misses, spec_states=0):
         """... and the exploration of a list of misses (numpy uint32, 16 words per record)"""
@@ -295,11 +315,10 @@ class Program:
             out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=inp.device)
         s = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
         m = ctypes.c_size_t()
-        with torch.cuda.device(inp.device):
-            rc = lib().trre_scan_device(self._h, inp.data_ptr(), n, out.data_ptr(), out.numel(), ctypes.byref(m), s)
-            if rc == E_CAPACITY:                       # variable-length output: retry with the size asked for
-                out = torch.empty(m.value + 16, dtype=torch.uint8, device=inp.device)
-                rc = lib().trre_scan_device(self._h, inp.data_ptr(), n, out.data_ptr(), out.numel(), ctypes.byref(m), s)
+
+        def call(o):
+            return lib().trre_scan_device(self._h, inp.data_ptr(), n, o.data_ptr(), o.numel(), ctypes.byref(m), s)
+        rc, out = _retry_capacity(call, out, m, inp.device)
         if rc == E_DIVERGES:
             raise TrreError(rc, lib().trre_last_error().decode("latin-1"), out[:m.value])
         _check(rc)
@@ -310,12 +329,8 @@ class Program:
         values[offsets[i]:offsets[i+1]] (offsets: 1-D int64 CUDA tensor, nrec + 1 entries, from 0 to values.numel()).  Each
         record is scanned as if it were a file of its own.  Returns (out_values, out_offsets): record i's output is
         out_values[out_offsets[i]:out_offsets[i+1]].  out may be values itself (in place); a too small out is replaced."""
-        import torch
         n, nrec, s = _column(values, offsets, stream)
-        if out is None:
-            out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
-        if out_offsets is None:
-            out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        out, out_offsets = _default_outputs(out, out_offsets, n, nrec, values.device)
         m = ctypes.c_size_t()
 
         def call(o):
@@ -334,12 +349,8 @@ class Program:
         the framing newline (b"cat" under [a:A-z:Z] gives b"CAT"; an empty string gives what an empty line prints).  Returns
         (out_values, out_offsets): string i's output is out_values[out_offsets[i]:out_offsets[i+1]].  out may be values itself
         (in place); a too small out is replaced.  A string the reference does not survive raises TrreError with partial=None."""
-        import torch
         n, nrec, s = _column(values, offsets, stream)
-        if out is None:
-            out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
-        if out_offsets is None:
-            out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        out, out_offsets = _default_outputs(out, out_offsets, n, nrec, values.device)
         m = ctypes.c_size_t()
 
         def call(o):
@@ -365,10 +376,7 @@ class Program:
         (uint8, 8 * ceil(nrec / 64) bytes, bit i & 7 of byte i >> 3).  out may be values itself; a too small out is replaced."""
         import torch
         n, nrec, s = _column(values, offsets, stream)
-        if out is None:
-            out = torch.empty(max(n, 1) + 16, dtype=torch.uint8, device=values.device)
-        if out_offsets is None:
-            out_offsets = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
+        out, out_offsets = _default_outputs(out, out_offsets, n, nrec, values.device)
         words = torch.zeros(max((nrec + 63) // 64, 1), dtype=torch.int64, device=values.device)     # (8-byte aligned)
         m, k = ctypes.c_size_t(), ctypes.c_size_t()
 
@@ -377,21 +385,13 @@ class Program:
                                                    out_offsets.data_ptr(), words.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
         rc, out = _retry_capacity(call, out, m, values.device)
         _check(rc)
-        bitmap = words.view(torch.uint8)[:8 * ((nrec + 63) // 64)]
-        if packed:
-            return out[:m.value], out_offsets, bitmap
-        shifts = torch.arange(8, dtype=torch.uint8, device=values.device)
-        valid = ((bitmap.unsqueeze(1) >> shifts) & 1).to(torch.bool).flatten()[:nrec]
-        return out[:m.value], out_offsets, valid
+        return out[:m.value], out_offsets, _validity(words, nrec, packed)
 
     def match_list(self, records, device=0):
         """list of bytes in -> list out: what an accepted string becomes (bytes), None for a rejected one (through match_strings)"""
         recs, off, values, offsets = _pack(records, device)
         out, out_off, valid = self.match_strings(values, offsets)
-        blob = out.cpu().numpy().tobytes()
-        o = out_off.cpu().numpy().tolist()
-        ok = valid.cpu().numpy().tolist()
-        return [blob[o[i]:o[i + 1]] if ok[i] else None for i in range(len(recs))]
+        return [b if ok else None for b, ok in zip(_read_back(out, out_off), valid.cpu().numpy().tolist())]
 
     def find_strings(self, values, offsets, stream=None):
         """Found strings (trre_find_device_strings; a program compiled with mode="find"): values and offsets as for
@@ -406,36 +406,29 @@ class Program:
         def call(o, cap, mo, mcap):
             return lib().trre_find_device_strings(self._h, values.data_ptr(), n, offsets.data_ptr(), nrec, o, cap, mo, mcap,
                                                   list_off.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(None, 0, None, 0)
-            if rc not in (0, E_CAPACITY):
-                _check(rc)
-            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
-            match_off = torch.zeros(k.value + 1, dtype=torch.int64, device=values.device)
-            if rc == E_CAPACITY:
-                _check(call(out.data_ptr(), m.value, match_off.data_ptr(), k.value))
-        return out[:m.value], match_off, list_off
+
+        def alloc(k, m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
+            match_off = torch.zeros(k + 1, dtype=torch.int64, device=values.device)
+            return (out[:m], match_off, list_off), (out.data_ptr(), m, match_off.data_ptr(), k)
+        return _query_then_fill(call, (None, 0, None, 0), alloc, (k, m), values.device)
 
     def find_list(self, records, device=0):
         """list of bytes in -> list of lists of bytes out: every match's output, string by string (through find_strings)"""
         recs, off, values, offsets = _pack(records, device)
-        out, match_off, list_off = self.find_strings(values, offsets)
-        blob = out.cpu().numpy().tobytes()
-        mo = match_off.cpu().numpy().tolist()
-        lo = list_off.cpu().numpy().tolist()
-        return [[blob[mo[j]:mo[j + 1]] for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
+        return _read_back(*self.find_strings(values, offsets))
 
-    def _span_call(self, values, offsets, starts, ends, cap, stream):
-        """one trre_span_device_strings call: (rc, n_matches, list_offsets)"""
+    def _span_call(self, values, offsets, stream):
+        """trre_span_device_strings on a column: (call(d_start, d_end, span_cap) -> rc, *n_matches, list_offsets)"""
         import torch
         n, nrec, s = _column(values, offsets, stream)
         list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
         k = ctypes.c_size_t()
-        with torch.cuda.device(values.device):
-            rc = lib().trre_span_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec,
-                                                starts.data_ptr() if cap else None, ends.data_ptr() if cap else None, cap,
-                                                list_off.data_ptr(), ctypes.byref(k), s)
-        return rc, k.value, list_off
+
+        def call(st, en, cap):
+            return lib().trre_span_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, st, en, cap,
+                                                  list_off.data_ptr(), ctypes.byref(k), s)
+        return call, k, list_off
 
     def span_strings(self, values, offsets, stream=None):
         """Match spans (trre_span_device_strings; a program compiled with mode="spans"): values and offsets as for scan_strings,
@@ -443,20 +436,20 @@ class Program:
         .. list_offsets[i + 1] - 1, and match j is values[starts[j]:ends[j]] — positions in values, absolute.  Two calls: the
         size query, then the one that fills arrays of exactly that size."""
         import torch
-        rc, k, list_off = self._span_call(values, offsets, None, None, 0, stream)
-        if rc not in (0, E_CAPACITY):
-            _check(rc)
-        starts = torch.empty(k, dtype=torch.int64, device=values.device)
-        ends = torch.empty(k, dtype=torch.int64, device=values.device)
-        if rc == E_CAPACITY:
-            rc, k2, list_off = self._span_call(values, offsets, starts, ends, k, stream)
-            _check(rc)
-            assert k2 == k
-        return starts, ends, list_off
+        call, k, list_off = self._span_call(values, offsets, stream)
+
+        def alloc(k):
+            starts = torch.empty(k, dtype=torch.int64, device=values.device)
+            ends = torch.empty(k, dtype=torch.int64, device=values.device)
+            return (starts, ends, list_off), (starts.data_ptr(), ends.data_ptr(), k)
+        return _query_then_fill(call, (None, None, 0), alloc, (k,), values.device)
 
     def count_strings(self, values, offsets, stream=None):
         """matches per string (str.count; > 0: str.contains), int64 — the size query alone: no span is stored"""
-        rc, _, list_off = self._span_call(values, offsets, None, None, 0, stream)
+        import torch
+        call, _, list_off = self._span_call(values, offsets, stream)
+        with torch.cuda.device(values.device):
+            rc = call(None, None, 0)
         if rc not in (0, E_CAPACITY):
             _check(rc)
         return list_off[1:] - list_off[:-1]
@@ -483,24 +476,17 @@ class Program:
         def call(o, cap, po, pcap):
             return lib().trre_split_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, o, cap, po, pcap,
                                                    list_off.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(None, 0, None, 0)
-            if rc not in (0, E_CAPACITY):
-                _check(rc)
-            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
-            piece_off = torch.zeros(k.value + 1, dtype=torch.int64, device=values.device)
-            if rc == E_CAPACITY:
-                _check(call(out.data_ptr(), m.value, piece_off.data_ptr(), k.value))
-        return out[:m.value], piece_off, list_off
+
+        def alloc(k, m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
+            piece_off = torch.zeros(k + 1, dtype=torch.int64, device=values.device)
+            return (out[:m], piece_off, list_off), (out.data_ptr(), m, piece_off.data_ptr(), k)
+        return _query_then_fill(call, (None, 0, None, 0), alloc, (k, m), values.device)
 
     def split_list(self, records, device=0):
         """list of bytes in -> per string the list of its pieces (bytes), as re.split gives them (through split_strings)"""
         recs, off, values, offsets = _pack(records, device)
-        out, piece_off, list_off = self.split_strings(values, offsets)
-        blob = out.cpu().numpy().tobytes()
-        po = piece_off.cpu().numpy().tolist()
-        lo = list_off.cpu().numpy().tolist()
-        return [[blob[po[j]:po[j + 1]] for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
+        return _read_back(*self.split_strings(values, offsets))
 
     def filter_strings(self, values, offsets, invert=False, stream=None):
         """Filtered strings (trre_filter_device_strings; a program compiled with mode="spans"): values and offsets as for
@@ -517,24 +503,19 @@ class Program:
         def call(o, cap, oo, rows, rcap):
             return lib().trre_filter_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, flags, o, cap, oo, rows,
                                                     rcap, ctypes.byref(k), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(None, 0, None, None, 0)
-            if rc not in (0, E_CAPACITY):
-                _check(rc)
-            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
-            out_off = torch.zeros(k.value + 1, dtype=torch.int64, device=values.device)
-            rows = torch.empty(k.value, dtype=torch.int64, device=values.device)
-            if rc == E_CAPACITY:
-                _check(call(out.data_ptr(), m.value, out_off.data_ptr(), rows.data_ptr(), k.value))
-        return out[:m.value], out_off, rows
+
+        def alloc(k, m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
+            out_off = torch.zeros(k + 1, dtype=torch.int64, device=values.device)
+            rows = torch.empty(k, dtype=torch.int64, device=values.device)
+            return (out[:m], out_off, rows), (out.data_ptr(), m, out_off.data_ptr(), rows.data_ptr(), k)
+        return _query_then_fill(call, (None, 0, None, None, 0), alloc, (k, m), values.device)
 
     def filter_list(self, records, invert=False, device=0):
         """list of bytes in -> (the kept strings, their indices in the list) (through filter_strings)"""
         recs, off, values, offsets = _pack(records, device)
         out, out_off, rows = self.filter_strings(values, offsets, invert=invert)
-        blob = out.cpu().numpy().tobytes()
-        o = out_off.cpu().numpy().tolist()
-        return [blob[o[r]:o[r + 1]] for r in range(len(o) - 1)], rows.cpu().numpy().tolist()
+        return _read_back(out, out_off), rows.cpu().numpy().tolist()
 
     def field_strings(self, values, offsets, k, stream=None, packed=False):
         """Field k of every string (trre_field_device_strings; a program compiled with mode="spans"): values and offsets as for
@@ -552,38 +533,24 @@ class Program:
         def call(o, cap, oo):
             return lib().trre_field_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, k, o, cap, oo,
                                                    words.data_ptr(), ctypes.byref(v), ctypes.byref(m), s)
-        with torch.cuda.device(values.device):
-            rc = call(None, 0, None)
-            if rc not in (0, E_CAPACITY):
-                _check(rc)
-            out = torch.empty(m.value + 16, dtype=torch.uint8, device=values.device)
+
+        def alloc(v, m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
             out_off = torch.zeros(nrec + 1, dtype=torch.int64, device=values.device)     # (no field has bytes: all zero, as they are)
-            if rc == E_CAPACITY:
-                _check(call(out.data_ptr(), m.value, out_off.data_ptr()))
-        bitmap = words.view(torch.uint8)[:8 * ((nrec + 63) // 64)]
-        if packed:
-            return out[:m.value], out_off, bitmap
-        shifts = torch.arange(8, dtype=torch.uint8, device=values.device)
-        valid = ((bitmap.unsqueeze(1) >> shifts) & 1).to(torch.bool).flatten()[:nrec]
-        return out[:m.value], out_off, valid
+            return (out[:m], out_off), (out.data_ptr(), m, out_off.data_ptr())
+        return _query_then_fill(call, (None, 0, None), alloc, (v, m), values.device) + (_validity(words, nrec, packed),)
 
     def field_list(self, records, k, device=0):
         """list of bytes in -> list out: field k of every string (bytes), None where the string has no such piece (through
         field_strings)"""
         recs, off, values, offsets = _pack(records, device)
         out, out_off, valid = self.field_strings(values, offsets, k)
-        blob = out.cpu().numpy().tobytes()
-        o = out_off.cpu().numpy().tolist()
-        ok = valid.cpu().numpy().tolist()
-        return [blob[o[i]:o[i + 1]] if ok[i] else None for i in range(len(recs))]
+        return [b if ok else None for b, ok in zip(_read_back(out, out_off), valid.cpu().numpy().tolist())]
 
     @staticmethod
     def _map_list(records, device, scan):
         recs, off, values, offsets = _pack(records, device)
-        out, out_off = scan(values, offsets)
-        blob = out.cpu().numpy().tobytes()
-        o = out_off.cpu().numpy().tolist()
-        return [blob[o[i]:o[i + 1]] for i in range(len(recs))]
+        return _read_back(*scan(values, offsets))
 
     def enqueue(self, inp, out, stream=None):
         import torch
