@@ -27,6 +27,7 @@ using namespace trre;
 namespace {
 
 int g_last_rounds = 0;       // repair rounds of the last exact-sub-range run (shim_last_rounds)
+std::vector<uint32_t> g_last_redo;   // the lanes the last window run handed to the redo pass, in the order they were listed (shim_last_redo)
 
 constexpr uint32_t kFlagG16SlowBit = 1u << 3;    // front.hpp: kFlagG16Slow
 using GeoTiny = Geometry<4, 64, 32>;
@@ -603,6 +604,7 @@ void run_lpw_t(const ScanArgs& a, int64_t lane_bytes, uint32_t& status) {
             if (L[lid].seen & kLpwDiv) status |= kStDiverge;
         }
     }
+    g_last_redo.assign(redo.begin() + 1, redo.begin() + 1 + redo[0]);
     // second launch: the lanes that touch an end of the input
     const StreamView TS = direct_view(a);
     alignas(16) uint8_t ring[kRingStride];
@@ -649,7 +651,8 @@ extern "C" {
 // family: 1 bytemap, 2 tile LP, 3 tile general (4 / 5, the LDS-tile walkers of the stream tables, went in round 6).
 // 20 / 21 stream LP by the emit pass alone (16-byte / 8-byte entries),
 // 8 positional-window stream LP, 9 direct stream general on the 8-byte entries (7 prefers the 16-byte ones), 6 direct stream LP, 7 direct stream general (geo: 0 -> 2048-byte lanes, 1 -> 48-byte lanes).
-// geo: 0 production, 1 tiny; 2 (the exact sub-ranges, families 32 / 33 and 17 / 18): lanes of 128 bytes in workgroups of 256.
+// geo: 0 production, 1 tiny; 2 (the exact sub-ranges, families 32 / 33 and 17 / 18, and the window families 8 / 26): lanes of 128 bytes, the
+// smallest the runtime accepts (the exact families: in workgroups of 256).
 // in_mis/out_mis: address misalignment (0..15) to give the staged buffers.
 // want_scratch: pass a mask scratch to the NFT long-line path.
 int shim_scan(const uint8_t* blob, int engine, int mask_bytes, int family, int geo, const uint8_t* in, size_t n,
@@ -677,14 +680,14 @@ int shim_scan(const uint8_t* blob, int engine, int mask_bytes, int family, int g
     else if (family == 8) {
         if (reinterpret_cast<const StreamBlobHeader*>(blob)->lpw_bytes == 0) return -5;
         // like the runtime: buffers that are not congruent mod 16 go to the direct walker
-        if (reinterpret_cast<uintptr_t>(a.out_v0) & 15u) run_direct_lp<>(a, geo == 0 ? 2048 : 48, status);
-        else run_lpw(a, geo == 0 ? 2048 : 64, status);
+        if (reinterpret_cast<uintptr_t>(a.out_v0) & 15u) run_direct_lp<>(a, geo == 0 ? 2048 : geo == 2 ? 128 : 48, status);
+        else run_lpw(a, geo == 0 ? 2048 : geo == 2 ? 128 : 64, status);
         total = n;
     }
     else if (family == 26) {                          // the window kernel on the pair form of its entries
         if (reinterpret_cast<const StreamBlobHeader*>(blob)->lpw2_bytes == 0) return -5;
-        if (reinterpret_cast<uintptr_t>(a.out_v0) & 15u) run_direct_lp<>(a, geo == 0 ? 2048 : 48, status);
-        else run_lpw(a, geo == 0 ? 2048 : 64, status, true);
+        if (reinterpret_cast<uintptr_t>(a.out_v0) & 15u) run_direct_lp<>(a, geo == 0 ? 2048 : geo == 2 ? 128 : 48, status);
+        else run_lpw(a, geo == 0 ? 2048 : geo == 2 ? 128 : 64, status, true);
         total = n;
     }
     else if (family == 6) { run_direct_lp<>(a, geo == 0 ? 2048 : 48, status); total = n; }
@@ -1068,6 +1071,11 @@ int shim_guard(const uint8_t* kblob, const uint8_t* in, size_t n, int in_mis, ui
 }
 
 int shim_last_rounds() { return g_last_rounds; }
+// the lanes the last run of a window family (8 / 26) handed to the redo pass: their number; the first `cap` of them go to `lanes`
+int shim_last_redo(uint32_t* lanes, int cap) {
+    for (int k = 0; k < cap && k < (int)g_last_redo.size(); ++k) lanes[k] = g_last_redo[k];
+    return (int)g_last_redo.size();
+}
 
 int shim_rev_sweep(const uint8_t* rblob, int geo, const uint8_t* in, size_t n, int in_mis, uint8_t* sym_out) {
     if (n == 0) return 0;

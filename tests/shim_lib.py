@@ -45,6 +45,7 @@ def lib():
         L.shim_lazy_round.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_int]
+        L.shim_last_redo.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
         _lib = L
     return _lib
 
@@ -162,6 +163,14 @@ def shim_scan_guided(prog, family, data, geo=1, in_mis=0, out_mis=0):
 def last_rounds():
     """repair rounds of the last exact-sub-range run on the shim"""
     return lib().shim_last_rounds()
+
+
+def last_redo():
+    """the lanes the last run of a window family (8, STREAM_LPW_PAIR) handed to the redo pass, ascending"""
+    n = lib().shim_last_redo(None, 0)
+    lanes = (ctypes.c_uint32 * max(n, 1))()
+    lib().shim_last_redo(lanes, n)
+    return sorted(lanes[:n])
 
 
 def scan_guided_like_runtime(prog, data, geo=1, family=GUIDED_LP, in_mis=0, out_mis=0):

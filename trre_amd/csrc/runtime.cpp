@@ -1055,6 +1055,11 @@ int route_window(trre_prog* p, ScanCtx* cx, LaunchPlan& pl, hipStream_t stream) 
     HIP_TRY(cx->d_redo.reserve((size_t)n_lanes, (size_t)(n_lanes + 1) * 4));
     HIP_TRY(hipMemsetAsync(cx->d_redo, 0, 4, stream));
     pl.args.redo = cx->d_redo;
+    // (TRRE_TRACE=1: the route and the form of the entries launch_lpw_kernel chooses — the pair form is only built for narrow entries and
+    // never larger than the kernel's LDS room (stream_pack.cpp) —; finish_inner adds how many lanes the redo pass took)
+    if (switches().trace)
+        fprintf(stderr, "trre: window kernel: %lld lane(s) of %lld bytes, %s entries\n", (long long)n_lanes, (long long)pl.lane_bytes,
+                p->stt.lpw2_ok && !switches().no_lpw_pair ? "pair" : (p->stt.lpw_delay > 3 ? "wide" : "narrow"));
     // (the pair form of the window entries where the tables have it: two input bytes per table read.  TRRE_NO_LPW_PAIR=1: A/B runs)
     launch_lpw_kernel((int)(p->stt.lpw.size() * 4), p->stt.lpw_delay > 3, pl.direct_ent_lds, pl.args, pl.lane_bytes, stream,
                       p->stt.lpw2_ok && !switches().no_lpw_pair ? (int)(p->stt.lpw2.size() * 4) : 0);
@@ -1626,6 +1631,12 @@ int finish_inner(trre_prog* p, DeviceState* st, ScanCtx* cx, size_t* out_len) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, cx->ev0, cx->ev1));
         p->last_ms = ms / (float)(was.count > 0 ? was.count : 1);   // average per launch of the batch
+    }
+    if (switches().trace && was.launched && was.plan.window) {
+        // (the stream is idle: the redo list is the last launch's.  One 4-byte copy, only when tracing)
+        uint32_t redone = 0;
+        HIP_TRY(hipMemcpy(&redone, cx->d_redo, 4, hipMemcpyDeviceToHost));
+        fprintf(stderr, "trre: window kernel: %u lane(s) redone, status 0x%x\n", redone, status);
     }
     rc = was.family == TRRE_KERNEL_DFT_LAZY ? lazy_rounds(f, &status) : kGoOn;
     if (rc == kGoOn && was.exact && !(status & (kStOverflow | kStDiverge))) rc = exact_repair(f, &status);
