@@ -58,6 +58,9 @@ extern "C" {
                            * trre_span_device_strings, trre_split_device_strings, trre_filter_device_strings,
                            * trre_field_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and
                            * stay TRRE_E_ARG, as they were) */
+#define TRRE_MODE_SUB 16 /* the first n matches of every string replaced by what they print, the rest of the string kept
+                          * (sed 's/x/y/', re.sub(p, r, s, count), str.replace(p, r, n)): the spans table and the texts table over the
+                          * same attempts.  NFT engine only; runs through trre_sub_device_strings and nothing else */
 
 /* return codes */
 #define TRRE_OK 0
@@ -147,7 +150,7 @@ int trre_set_kernel(trre_prog* p, int kernel_family); /* force a family (benchma
  * tests).  Returns the blob size; copies min(size, cap) bytes. */
 size_t trre_export_tables(const trre_prog* p, void* buf, size_t cap);
 size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap); /* 0 if the pattern does not fold */
-size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted, 5 / 6 (find mode) the texts / the marks forward tables, both over the backward DFA of 0, 7 (spans mode) the markers' forward table, over the backward DFA of 0; 0 if none */
+size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap); /* which: 0 backward DFA, 1 forward tables, 4 (match mode) a byte per backward state: 1 where a line that starts with that symbol is accepted, 5 / 6 (find mode) the texts / the marks forward tables, both over the backward DFA of 0, 7 (spans mode) the markers' forward table, over the backward DFA of 0; a sub program answers 0 and 7 as a spans program and 5 with its inner texts table; 0 if none */
 
 /* Replaces the scan branch of main() (trre_nft.c:775-790 / trre_dft.c:1272-1286)
  * for a whole buffer that is already resident in HBM.
@@ -437,6 +440,50 @@ int trre_filter_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, cons
 int trre_field_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k,
                               uint8_t* d_out, size_t cap, int64_t* d_out_off, uint8_t* d_valid, size_t* n_valid,
                               size_t* out_len, void* stream);
+
+/* Replaced strings: the same column of strings under a program compiled with TRRE_MODE_SUB, with SOME of every string's matches
+ * replaced by what they print — sed 's/x/y/' (the first match only), re.sub(p, r, s, count), s.str.replace(p, r, n=1), SQL's
+ * regexp_replace(s, p, r, 1, k) (the k-th occurrence only), sed 's/x/y/2g' (from the second on).  String i has bytes s; L is s
+ * cut at its first NUL; the scan loop's attempts on L are exactly those of trre_span_device_strings and
+ * trre_find_device_strings: matches (s_r, e_r), r = 0 .. c - 1, ordered and disjoint, each with the output o_r that the find call
+ * defines (what fputs prints: an output that holds a NUL ends before it).  Match r of its string is SELECTED exactly when
+ * first <= r and (count < 0 or r - first < count) — compared, never added: any count is legal, count == 0 selects nothing, and
+ * first < 0 is TRRE_E_ARG.  out_i is s with the bytes s[s_r .. e_r) of every selected match replaced by o_r; everything else
+ * stays: the gaps, the unselected matches, and a NUL with everything behind it (as the split and field calls keep it).  An empty
+ * selected match inserts o_r at its position ('x*:y' on "bb": (0, -1) gives "ybyby", (0, 1) "ybb", (2, 1) "bby", (3, 1) "bb").
+ * Two identities: for a string without a NUL, (first, count) = (0, -1) is byte for byte what trre_scan_device_strings returns
+ * for the same pattern compiled in scan mode on the NFT engine; with nothing selected d_out is d_in and
+ * d_out_off[i] = d_off[i] - d_off[0].
+ *   d_out        cap bytes: the outputs, concatenated in input order; *out_len is their total (longer or shorter than n)
+ *   d_out_off    nrec + 1 entries: d_out_off[0] = 0, d_out_off[nrec] = *out_len
+ *   *n_replaced  (may be null) the number of selected matches in the column;  *out_len may be null
+ * d_out may be null only with cap == 0, and d_out_off only when d_out is: that is the size query.  nrec == 0 is valid with
+ * n == 0: TRRE_OK, and d_out_off[0] = 0 if d_out_off is not null.  The offsets' check (TRRE_E_ARG, nothing written), a string that
+ * holds a '\n' (TRRE_E_ARG, found on the device before anything of the caller's is written) and a split-form scan in flight: as
+ * for trre_span_device_strings.  Any overlap among d_in, d_off, d_out and d_out_off: TRRE_E_ARG — there is no in-place form.
+ * Refused before the device is touched: a null argument, a program not compiled with TRRE_MODE_SUB (TRRE_E_ARG) — and a sub
+ * program given to any other scan or column call is TRRE_E_ARG there —; a program that can print a '\n' of its own
+ * (TRRE_E_UNSUPPORTED: the framed texts could not be told apart); TRRE_KERNEL_BACKTRACK forced through trre_set_kernel
+ * (TRRE_E_UNSUPPORTED); first < 0, 2^55 strings or bytes (TRRE_E_ARG).
+ *   TRRE_E_CAPACITY  exactly when *out_len > cap: *out_len and *n_replaced are valid; d_out and d_out_off have not been written
+ *                    at all, and a retry with that room succeeds.
+ *   TRRE_E_DIVERGES  from either scan: *out_len = *n_replaced = 0; trre_last_error() holds the reference's message.
+ *   TRRE_E_DEVICE    the two scans disagree on the number of matches (internal), before anything of the caller's is written.
+ * How: the span call's passes and its emit pass into arrays of the library's own (where every match starts and ends, the list
+ * offsets); the find call's texts scan of the SAME staged text under the inner program's table, unframed into the library's
+ * own buffer with the texts' offsets.  One pass over the matches finds each match's string by a binary search in the list
+ * offsets, its rank there and so whether it is selected, and leaves per chunk of 1 024 matches the selected matches, their
+ * texts' bytes and their matched bytes; three exclusive sums, whose totals give *n_replaced and
+ * *out_len = n - matched + texts, read back in one synchronisation: the capacity decision.  A second pass over the matches
+ * stores the output position at which each match's place begins; a pass over the strings stores d_out_off; and one
+ * output-driven splice writes d_out in 16 KiB tiles of its own address space as whole aligned 16-byte vectors, every vector
+ * filled from the alternating sources — a text, then the input up to the next match — which it finds by a binary search among
+ * the places (the tile's window of them in LDS when it fits).  Every byte and word is stored once.
+ * Device memory, kept by the (prog, device) until trre_free: the span call's, the inner program's framed texts, the texts
+ * unframed, and 32 bytes per match.  Synchronous with respect to `stream`; trre_last_scan_flags as for the strings call. */
+int trre_sub_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t first,
+                            int64_t count, uint8_t* d_out, size_t cap, int64_t* d_out_off, size_t* n_replaced, size_t* out_len,
+                            void* stream);
 
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */

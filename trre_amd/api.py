@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("TRRE_LIB_PATH") or os.path.join(_HERE, "lib", "libtrr
 
 ENGINE_NFT, ENGINE_DFT = 0, 1
 MODE_SCAN, MODE_MATCH, MODE_SCAN_ALL, MODE_MATCH_ALL, MODE_FIND, MODE_SPANS = 0, 1, 2, 3, 4, 8
+MODE_SUB = 16
 _ENGINES = {"nft": ENGINE_NFT, "dft": ENGINE_DFT, ENGINE_NFT: ENGINE_NFT, ENGINE_DFT: ENGINE_DFT}
 
 KERNEL_AUTO, KERNEL_BYTEMAP, KERNEL_TILE_LP, KERNEL_TILE_GEN, KERNEL_STREAM_LP, KERNEL_STREAM_GEN = 0, 1, 2, 3, 4, 5
@@ -102,6 +103,7 @@ def lib():
         L.trre_split_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_filter_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_field_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_sub_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_int64, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -225,11 +227,12 @@ class Program:
         string as a list per string (find_strings / find_list, NFT engine), or "spans": where every match of every string starts
         and ends (span_strings / span_list / count_strings, NFT engine) and the pieces between the matches (split_strings /
         split_list), the strings with a match or without one (filter_strings / filter_list) and one piece of every string
-        (field_strings / field_list)"""
+        (field_strings / field_list), or "sub": the first n matches of every string replaced by what they print (sub_strings /
+        sub_list, NFT engine)"""
         self.pattern = _bytes(pattern)
         self.engine = _ENGINES[engine]
         self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL,
-                     "find": MODE_FIND, "spans": MODE_SPANS}.get(mode, mode)
+                     "find": MODE_FIND, "spans": MODE_SPANS, "sub": MODE_SUB}.get(mode, mode)
         self._h = ctypes.c_void_p()
         _check(lib().trre_compile_mode(self.pattern, len(self.pattern), self.engine, self.mode, ctypes.byref(self._h)))
 
@@ -546,6 +549,33 @@ class Program:
         recs, off, values, offsets = _pack(records, device)
         out, out_off, valid = self.field_strings(values, offsets, k)
         return [b if ok else None for b, ok in zip(_read_back(out, out_off), valid.cpu().numpy().tolist())]
+
+    def sub_strings(self, values, offsets, count=-1, first=0, stream=None):
+        """Some of every string's matches replaced by what they print (trre_sub_device_strings; a program compiled with
+        mode="sub"): values and offsets as for scan_strings, no string holding a b"\\n".  Match r of its string (r = 0, 1, ..) is
+        replaced when first <= r and (count < 0 or r - first < count): count=1 is sed's s/x/y/ and re.sub(.., count=1), first=k
+        with count=1 the k-th occurrence only, first=k with count=-1 every one from the k-th on; the defaults replace all.
+        Everything else of the string stays, a NUL and what is behind it included.  Returns (out, out_offsets): string i's
+        output is out[out_offsets[i]:out_offsets[i + 1]].  Two calls: the size query, then the one that fills a buffer of
+        exactly that size."""
+        import torch
+        n, nrec, s = _column(values, offsets, stream)
+        m, r = ctypes.c_size_t(), ctypes.c_size_t()
+
+        def call(o, cap, oo):
+            return lib().trre_sub_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, first, count, o, cap, oo,
+                                                 ctypes.byref(r), ctypes.byref(m), s)
+
+        def alloc(r, m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
+            out_off = torch.zeros(nrec + 1, dtype=torch.int64, device=values.device)     # (every output empty: all zero, as they are)
+            return (out[:m], out_off), (out.data_ptr(), m, out_off.data_ptr())
+        return _query_then_fill(call, (None, 0, None), alloc, (r, m), values.device)
+
+    def sub_list(self, records, count=-1, first=0, device=0):
+        """list of bytes in -> list of bytes out: every string with the selected matches replaced (through sub_strings)"""
+        recs, off, values, offsets = _pack(records, device)
+        return _read_back(*self.sub_strings(values, offsets, count=count, first=first))
 
     @staticmethod
     def _map_list(records, device, scan):

@@ -18,6 +18,7 @@ struct SpanArgs;
 struct SplitArgs;
 struct FilterArgs;
 struct FieldArgs;
+struct SubArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -131,6 +132,15 @@ void launch_filter_emit(const FilterArgs& a, void* stream);
 void launch_field_bounds(const SpanArgs& sp, const FieldArgs& a, void* stream);
 void launch_field_count(const FieldArgs& a, void* stream);
 void launch_field_emit(const FieldArgs& a, void* stream);
+// replaced strings (records_block.hpp), behind launch_span_emit's spans and list offsets and launch_find_unframe's texts: the
+// selection bits and the selected matches, texts' bytes and matched bytes per chunk of sub_chunk_matches() matches (a.cnt; a.status
+// |= 1 when the arrays are out of order); then — behind their three exclusive scans — where every segment starts; the output
+// offsets; the outputs' bytes (nothing is launched for an empty output)
+int64_t sub_chunk_matches();
+void launch_sub_plan(const SubArgs& a, void* stream);
+void launch_sub_place(const SubArgs& a, void* stream);
+void launch_sub_offsets(const SubArgs& a, void* stream);
+void launch_sub_emit(const SubArgs& a, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

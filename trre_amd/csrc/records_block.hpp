@@ -1179,4 +1179,234 @@ TRRE_HD void field_emit_offsets(const FieldArgs& a, const FilterTile<G>& t, int6
             a.f.out_off[i + 1] = k0 + (int64_t)filter_kept_below<G>(bits16, pv, a.f.off[i + 1] + a.f.vbeg - t.s0);
 }
 
+// ---- replaced strings (trre_sub_device_strings) ----------------------------------------------------------------------------
+// Some of every string's matches replaced by what they print: a splice of two sources the library already has.  The span call's
+// emit pass leaves, in arrays of the library's own, S[j], E[j] (where match j of the column starts and ends in d_in) and the list
+// offsets L[nrec + 1]; the find call's texts scan of the same staged text, unframed, leaves the texts X and XO[found + 1].  Match
+// j belongs to string i = the first i with L[i + 1] > j (strings without matches are skipped by the search itself), has rank
+// r = j - L[i] there, and is SELECTED when first <= r and (count < 0 or r - first < count).  With t_j the bytes of its text and
+// m_j = E[j] - S[j] when selected, both 0 when not, the output is
+//     in[0, S[0])   text 0   in[Ee[0], S[1])   text 1   in[Ee[1], S[2])   ...   text found-1   in[Ee[found-1], n)
+// Ee[j] = E[j] when selected and S[j] when not: an unselected match is an empty text in front of its own bytes.  SEGMENT j is
+// text j with the input behind it; it starts at output position
+//     P[j] = S[j] + sum over k < j of (t_k - m_k),       P[found] = out_len = n - sum m + sum t
+// Every array has one more entry in FRONT, index -1, for the bytes before the first match: P[-1] = 0, Ee[-1] = 0 with an empty
+// text; and S[found] = n closes the last segment.  So segment j, j in [-1, found), covers the output [P[j], P[j + 1]), its
+// text has (P[j + 1] - P[j]) - (S[j + 1] - Ee[j]) bytes at X + XO[j], and its input bytes start at Ee[j]: the emit pass needs
+// no selection bit.  The passes, over CHUNKS of THREADS * kSubPer consecutive matches (a thread has kSubPer in a row):
+//   k_sub_plan     the selection bit of every match, parked in P[j]; cnt[3][chunks]: the selected matches, their texts' bytes,
+//                  their matched bytes; and the check that the spans and the texts' offsets are ordered (a status word)
+//   k_chunk_scan   three times: base[3][chunks + 1]; the totals are n_replaced and out_len: the capacity decision
+//   k_sub_place    P[j] and Ee[j] (in place of E[j]) from the chunk's bases and a workgroup scan of the threads' sums; thread 0 of
+//                  chunk 0 stores P[-1], Ee[-1] = off[0], P[found] and S[found]
+//   k_sub_offsets  a thread per entry: out_off[i] = off[i] + (P[L[i]] - S[L[i]]), the growth before the string's first match
+//   k_sub_emit     output-driven, over tiles of TILE bytes of the OUTPUT's v-space (v = position + the address of out mod 16):
+//                  thread 0 finds the segments the tile touches by two binary searches in P; when that window of P fits, all
+//                  threads copy it into LDS; then a thread owns destination vectors (vector j * THREADS + tid of the tile:
+//                  coalesced), finds the segment of each one's first byte (an upper bound in P, minus one) and fills it.  A
+//                  whole vector inside one text or one run of input is one unaligned 16-byte read (two aligned loads and a
+//                  funnel shift) and one aligned 16-byte store; any other is put together piece by piece, and leaves a
+//                  segment for the next one that has bytes — the one behind it, or, behind a run of empty segments, an
+//                  upper bound in P again: 40 000 empty segments at one position cost one search, not 40 000 steps.
+// Who writes which byte and word: every P[j], Ee[j] the thread that owns match j; out_off[i] thread i; every output byte the
+// thread that owns its destination vector, once; the ragged first and last vectors of the buffer are byte stores, and nothing
+// at or behind out_len is stored.
+constexpr int kSubPer = 4;                            // matches per thread: chunks of 1 024
+constexpr int kSubWindow = 2048;                      // entries of P a tile keeps in LDS: 16 KiB
+
+struct SubArgs {
+    const uint8_t* in;      // the caller's d_in
+    int64_t n;
+    const int64_t* off;     // [nrec + 1] the caller's offsets
+    int64_t nrec;
+    const int64_t* L;       // [nrec + 1] the span call's list offsets
+    int64_t* S;             // [-1 .. found] where match j starts (k_span_emit); S[found] = n (k_sub_place)
+    int64_t* E;             // [-1 .. found) where it ends (k_span_emit), then the effective end Ee[j] (k_sub_place)
+    const int64_t* XO;      // [0 .. found] the texts' offsets (k_find_unframe)
+    const uint8_t* X;       // the texts
+    int64_t x_len;          // their bytes: XO[found]
+    int64_t* P;             // [-1 .. found] the selection bit (k_sub_plan), then where segment j starts in the output
+    int64_t found;
+    int64_t j0, out0;       // the first match and the output position of the column's start: 0 (the host shim: a column as if one came before)
+    int64_t first, count;
+    int64_t chunks;
+    uint64_t* cnt;          // [3][chunks] selected matches, their texts' bytes, their matched bytes
+    const uint64_t* base;   // [3][chunks + 1] their exclusive scans
+    uint32_t* status;       // |= 1: the spans or the texts' offsets are not ordered (internal)
+    uint8_t* out;           // [out_len]
+    int64_t out_len;
+    int64_t* out_off;       // [nrec + 1]
+};
+
+struct SubListKey {   // the matches before the end of string i
+    const int64_t* L;
+    TRRE_HD int64_t operator()(int64_t i) const { return L[i + 1]; }
+};
+struct SubPlaceKey {  // where segment k - 1 starts, k counted from the first one
+    const int64_t* Pz;
+    TRRE_HD int64_t operator()(int64_t k) const { return Pz[k]; }
+};
+TRRE_HD bool sub_selected(const SubArgs& a, int64_t r) { return a.first <= r && (a.count < 0 || r - a.first < a.count); }
+
+// k_sub_plan: the thread's kSubPer matches of chunk c: their selection bits into P, c3 = their three sums; returns 1 when an
+// array is out of order
+template <int THREADS>
+TRRE_HD uint32_t sub_plan_thread(const SubArgs& a, int64_t c, int tid, uint64_t (&c3)[3]) {
+    c3[0] = c3[1] = c3[2] = 0;
+    uint32_t bad = 0;
+    const int64_t j0 = (c * THREADS + tid) * kSubPer;
+    int64_t i = -1, iend = -1;                        // the string of the match before, and L[i + 1]
+    for (int64_t j = j0; j < j0 + kSubPer && j < a.found; ++j) {
+        if (j >= iend) {                              // (the string behind, where it has the match: short strings, a match or two each)
+            i = i >= 0 && i + 2 <= a.nrec && j < a.L[i + 2] ? i + 1 : rec_lower_bound(SubListKey{a.L}, a.nrec, j + 1);
+            if (i >= a.nrec) { bad = 1; break; }      // (never: L[nrec] = found)
+            iend = a.L[i + 1];
+        }
+        const int64_t s = a.S[j], e = a.E[j], next = j + 1 < a.found ? a.S[j + 1] : a.n;
+        const int64_t x0 = a.XO[j], x1 = a.XO[j + 1];
+        if (s < 0 || s > e || e > next || next > a.n || x0 < 0 || x0 > x1 || x1 > a.x_len || (j == a.j0 && x0 != 0)) bad = 1;
+        const bool sel = sub_selected(a, j - a.L[i]);
+        a.P[j] = sel ? 1 : 0;
+        if (sel) { c3[0] += 1; c3[1] += (uint64_t)(x1 - x0); c3[2] += (uint64_t)(e - s); }
+    }
+    return bad;
+}
+// k_sub_place: the thread's sums again, from the parked bits
+template <int THREADS>
+TRRE_HD void sub_place_sums(const SubArgs& a, int64_t c, int tid, uint64_t (&c3)[3]) {
+    c3[0] = c3[1] = c3[2] = 0;
+    const int64_t j0 = (c * THREADS + tid) * kSubPer;
+    for (int64_t j = j0; j < j0 + kSubPer && j < a.found; ++j)
+        if (a.P[j]) { c3[0] += 1; c3[1] += (uint64_t)(a.XO[j + 1] - a.XO[j]); c3[2] += (uint64_t)(a.E[j] - a.S[j]); }
+}
+// ... the same matches; pt, pm: the texts' and the matched bytes of the selected matches of the chunk before the thread's
+template <int THREADS>
+TRRE_HD void sub_place_thread(const SubArgs& a, int64_t c, int tid, uint64_t pt, uint64_t pm) {
+    int64_t grow = (int64_t)(a.base[a.chunks + 1 + c] + pt) - (int64_t)(a.base[2 * (a.chunks + 1) + c] + pm);
+    const int64_t j0 = (c * THREADS + tid) * kSubPer;
+    for (int64_t j = j0; j < j0 + kSubPer && j < a.found; ++j) {
+        const bool sel = a.P[j] != 0;
+        a.P[j] = a.S[j] + grow;
+        if (sel) grow += (a.XO[j + 1] - a.XO[j]) - (a.E[j] - a.S[j]);
+        else a.E[j] = a.S[j];
+    }
+    if (j0 == a.j0) {
+        a.P[a.j0 - 1] = a.out0; a.E[a.j0 - 1] = a.off[0];
+        a.P[a.found] = a.out_len; a.S[a.found] = a.n;
+    }
+}
+// k_sub_offsets: entry i of the output offsets, i in [0, nrec]
+TRRE_HD void sub_offset(const SubArgs& a, int64_t i) {
+    const int64_t j = a.L[i];
+    a.out_off[i] = a.off[i] + (a.P[j] - a.S[j]);
+}
+
+// k_sub_emit.  The segments are counted from 0 here: k = j + 1, over Pz = P - 1 [found + 2], Sz = S - 1, Ez = E - 1, XOz = XO - 1
+template <class G>
+struct SubTile {
+    int A;                  // the address of out mod 16
+    int64_t o0, o1;         // the tile's output positions
+    TRRE_HD SubTile(const SubArgs& a, int64_t b) {
+        A = (int)(reinterpret_cast<uintptr_t>(a.out) & 15u);
+        o0 = b * G::TILE - A > a.out0 ? b * G::TILE - A : a.out0;
+        o1 = (b + 1) * G::TILE - A < a.out_len ? (b + 1) * G::TILE - A : a.out_len;
+    }
+};
+// the segment that holds output position o (o < out_len): the last k with Pz[k] <= o
+TRRE_HD int64_t sub_segment_of(const SubArgs& a, int64_t o) {
+    return a.j0 + rec_lower_bound(SubPlaceKey{a.P - 1 + a.j0}, a.found + 1 - a.j0, o + 1) - 1;
+}
+// thread 0: the segments [win[0], win[1]] the tile touches
+template <class G>
+TRRE_HD void sub_emit_window(const SubArgs& a, const SubTile<G>& t, int64_t* win) {
+    win[0] = sub_segment_of(a, t.o0);
+    win[1] = sub_segment_of(a, t.o1 - 1);
+}
+// all threads: Pz[win[0] .. win[1] + 1] into the image, when it fits
+template <class G>
+TRRE_HD void sub_keep_window(const SubArgs& a, const int64_t* win, int tid, int64_t* image) {
+    const int64_t cnt = win[1] - win[0] + 2;
+    if (cnt > kSubWindow) return;
+    for (int64_t k = tid; k < cnt; k += G::THREADS) image[k] = a.P[win[0] + k - 1];
+}
+// Pz through the tile's image where it has the entry
+struct SubPlaces {
+    const int64_t* Pz;
+    const int64_t* image;
+    int64_t k0, cnt;        // the image holds Pz[k0 .. k0 + cnt); cnt 0: no image
+    TRRE_HD int64_t operator()(int64_t k) const { return k >= k0 && k - k0 < cnt ? image[k - k0] : Pz[k]; }
+};
+template <class G>
+TRRE_HD SubPlaces sub_places(const SubArgs& a, const int64_t* win, const int64_t* image) {
+    const int64_t cnt = win[1] - win[0] + 2;
+    return SubPlaces{a.P - 1, image, win[0], cnt > kSubWindow ? 0 : cnt};
+}
+// the last k in [lo, hi] with Pz[k] <= o (Pz[lo] <= o)
+TRRE_HD int64_t sub_segment_in(const SubPlaces& pz, int64_t lo, int64_t hi, int64_t o) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo + 1) >> 1);
+        if (pz(mid) <= o) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// 16 bytes from any address whose 16 bytes are all readable: two aligned loads, funnel-shifted (str_funnel16's arithmetic)
+TRRE_HD U128 sub_load16u(const uint8_t* p) {
+    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
+    const U128* q = reinterpret_cast<const U128*>(p - sh);
+    const U128 lo = q[0];
+    if (sh == 0) return lo;
+    const U128 hi = q[1];
+    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    if (sh & 8u) { w[0] = w[2]; w[1] = w[3]; w[2] = w[4]; w[3] = w[5]; w[4] = w[6]; w[5] = w[7]; }
+    if (sh & 4u) { w[0] = w[1]; w[1] = w[2]; w[2] = w[3]; w[3] = w[4]; w[4] = w[5]; }
+    const uint32_t bs = (sh & 3u) * 8u;
+    U128 r;
+    r.x = (uint32_t)((((uint64_t)w[1] << 32) | w[0]) >> bs); r.y = (uint32_t)((((uint64_t)w[2] << 32) | w[1]) >> bs);
+    r.z = (uint32_t)((((uint64_t)w[3] << 32) | w[2]) >> bs); r.w = (uint32_t)((((uint64_t)w[4] << 32) | w[3]) >> bs);
+    return r;
+}
+// the thread's destination vectors of tile b
+template <class G>
+TRRE_HD void sub_emit_vecs(const SubArgs& a, const SubTile<G>& t, int64_t b, int tid, const int64_t* win, const int64_t* image) {
+    const SubPlaces pz = sub_places<G>(a, win, image);
+    const int64_t* Sz = a.S - 1;
+    const int64_t* Ez = a.E - 1;
+    const int64_t* XOz = a.XO - 1;
+    for (int j = 0; j < G::VECS; ++j) {
+        const int64_t v = b * G::TILE + 16 * ((int64_t)j * G::THREADS + tid);
+        const int64_t p0 = v - t.A > a.out0 ? v - t.A : a.out0, p1 = v + 16 - t.A < a.out_len ? v + 16 - t.A : a.out_len;
+        if (p1 <= p0) continue;
+        const int cnt = (int)(p1 - p0);
+        int64_t k = sub_segment_in(pz, win[0], win[1], p0);
+        int64_t beg = pz(k), end = pz(k + 1);
+        int64_t tl = (end - beg) - (Sz[k + 1] - Ez[k]);               // the segment's text bytes
+        uint8_t* d = a.out + p0;
+        if (cnt == 16 && p0 + 16 <= end && (p0 - beg >= tl || p0 - beg + 16 <= tl)) {
+            const int64_t at = p0 - beg;
+            rec_store16(d, sub_load16u(at >= tl ? a.in + Ez[k] + (at - tl) : a.X + XOz[k] + at));
+            continue;
+        }
+        U128 r;
+        r.x = r.y = r.z = r.w = 0;
+        int64_t o = p0;
+        for (int f = 0;;) {
+            const int64_t at = o - beg;
+            const int take = end - o < cnt - f ? (int)(end - o) : cnt - f;
+            const int64_t text = tl > 0 ? XOz[k] : 0, raw = Ez[k] - tl;
+            for (int x = 0; x < take; ++x) str_put_byte(r, f + x, at + x < tl ? a.X[text + at + x] : a.in[raw + at + x]);
+            f += take; o += take;
+            if (f >= cnt) break;
+            k = pz(k + 2) > o ? k + 1 : sub_segment_in(pz, k + 1, win[1], o);      // (o < out_len: segment k + 1 exists)
+            beg = pz(k); end = pz(k + 1);
+            tl = (end - beg) - (Sz[k + 1] - Ez[k]);
+        }
+        if (cnt == 16) {
+            rec_store16(d, r);
+        } else {
+            for (int x = 0; x < cnt; ++x) d[x] = (uint8_t)filter_get_byte(r, x);
+        }
+    }
+}
+
 }  // namespace trre

@@ -172,8 +172,11 @@ struct ScanCtx {
     DevBuf<uint64_t> d_match;         // trre_match_device_strings: accepted strings per group of 256, then their exclusive scan [groups + 1] (groups)
     DevBuf<int64_t> d_find_off;       // trre_find_device_strings: the list offsets while they are ranks and located positions [nrec + 1] (entries)
     DevBuf<uint8_t> d_find_marks;     // ... the marks scan unframed: a byte per match (bytes)
-    DevBuf<int64_t> d_filter_lists;   // trre_filter_device_strings, trre_field_device_strings: the span call's list offsets, which give the verdicts [nrec + 1] (entries)
+    DevBuf<int64_t> d_filter_lists;   // trre_filter_device_strings, trre_field_device_strings, trre_sub_device_strings: the span call's list offsets [nrec + 1] (entries)
     DevBuf<int64_t> d_field_bounds;   // trre_field_device_strings: where every string's field starts [nrec], then where it ends [nrec] (strings)
+    DevBuf<int64_t> d_sub_idx;        // trre_sub_device_strings: S, E, XO, P, each [found + 2] with entry -1 in front (matches)
+    DevBuf<uint8_t> d_sub_texts;      // ... the texts scan unframed (bytes)
+    DevBuf<uint64_t> d_sub_cnt;       // ... the status word, cnt [3][chunks], base [3][chunks + 1] (chunks)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
     DevBuf<uint32_t> d_cevents, d_chdr;
@@ -269,6 +272,8 @@ struct trre_prog {
     std::vector<uint8_t> ablob;       // match mode, guided tables: GuidedTables::accept as bits (32-bit words; trre_match_device_strings)
     std::unique_ptr<trre_prog> find_marks;    // find mode: this program holds the texts table (gt), the inner one the marks table over the same
                                               // backward DFA — a program of its own, with its own device state (trre_find_device_strings)
+    std::unique_ptr<trre_prog> sub_texts;     // sub mode: this program holds the markers' table of spans mode (gt) and the stack guard, the inner one
+                                              // the texts table of find mode over the same nodes (trre_sub_device_strings)
     int mask_bytes = 0;
     bool profiling = false;
     std::atomic<float> last_ms{-1.f};
@@ -524,6 +529,7 @@ int auto_family(const trre_prog& p) {
     using namespace trre;
     if (p.mode == TRRE_MODE_FIND) return TRRE_KERNEL_GUIDED_GEN;      // (both scans of trre_find_device_strings: their outputs are no one's input length)
     if (p.mode == TRRE_MODE_SPANS) return TRRE_KERNEL_GUIDED_GEN;     // (the scan of trre_span_device_strings: the table is never length-preserving)
+    if (p.mode == TRRE_MODE_SUB) return TRRE_KERNEL_GUIDED_GEN;       // (the spans scan of trre_sub_device_strings; its texts scan runs an inner find program)
     if (p.lazy_only) return TRRE_KERNEL_DFT_LAZY;      // beyond the eager construction's caps: the tables grow with the input (lazy_block.hpp)
     if (p.engine == TRRE_ENGINE_DFT && (p.dt.flags & kFlagMemoryless)) return TRRE_KERNEL_BYTEMAP;
     // a stream table too large for LDS is walked through L1/L2 (<= 0.35 TB/s); guided tables with a small forward table
@@ -664,12 +670,13 @@ constexpr const char* kFindOnlyMsg = "error: a program compiled with TRRE_MODE_F
 constexpr const char* kSpansOnlyMsg = "error: a program compiled with TRRE_MODE_SPANS runs through trre_span_device_strings, trre_split_device_strings, trre_filter_device_strings and trre_field_device_strings only";
 constexpr const char* kDivergeMsg = "error: stack max capacity reached (the reference's search does not terminate on this input)";
 // a program that one call alone runs: that call's name for every other call's refusal (null: any scan call may run it)
+constexpr const char* kSubOnlyMsg = "error: a program compiled with TRRE_MODE_SUB runs through trre_sub_device_strings only";
 const char* own_call_only(const trre_prog& p) {
-    return p.mode == TRRE_MODE_FIND ? kFindOnlyMsg : p.mode == TRRE_MODE_SPANS ? kSpansOnlyMsg : nullptr;
+    return p.mode == TRRE_MODE_FIND ? kFindOnlyMsg : p.mode == TRRE_MODE_SPANS ? kSpansOnlyMsg : p.mode == TRRE_MODE_SUB ? kSubOnlyMsg : nullptr;
 }
 bool guard_applies(const trre_prog& p, const ScanCtx& cx, size_t n) {
     return !trre::switches().no_stack_guard && p.guard.on && !cx.guard_off &&
-           (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH || p.mode == TRRE_MODE_FIND || p.mode == TRRE_MODE_SPANS) && n + 1 >= p.guard.l_min;
+           (p.mode == TRRE_MODE_SCAN || p.mode == TRRE_MODE_MATCH || p.mode == TRRE_MODE_FIND || p.mode == TRRE_MODE_SPANS || p.mode == TRRE_MODE_SUB) && n + 1 >= p.guard.l_min;
 }
 struct GuardHit {
     bool hit = false;
@@ -1743,8 +1750,10 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
     if (!out) return fail(TRRE_E_ARG, "error: null output handle");
     *out = nullptr;
     if (engine != TRRE_ENGINE_NFT && engine != TRRE_ENGINE_DFT) return fail(TRRE_E_ARG, "error: unknown engine");
-    if (mode != TRRE_MODE_SCAN && mode != TRRE_MODE_MATCH && mode != TRRE_MODE_FIND && mode != TRRE_MODE_SPANS && !is_generate(mode))
+    if (mode != TRRE_MODE_SCAN && mode != TRRE_MODE_MATCH && mode != TRRE_MODE_FIND && mode != TRRE_MODE_SPANS && mode != TRRE_MODE_SUB && !is_generate(mode))
         return fail(TRRE_E_ARG, "error: unknown mode");
+    if (mode == TRRE_MODE_SUB && engine != TRRE_ENGINE_NFT)
+        return fail(TRRE_E_UNSUPPORTED, "error: sub mode is offered for the non-deterministic engine only (the deterministic engine's matches cannot be told from its raw bytes by the reference)");
     if (mode == TRRE_MODE_SPANS && engine != TRRE_ENGINE_NFT)
         return fail(TRRE_E_UNSUPPORTED, "error: spans mode is offered for the non-deterministic engine only (the deterministic engine's matches cannot be told from its raw bytes by the reference)");
     if (mode == TRRE_MODE_FIND && engine != TRRE_ENGINE_NFT)
@@ -1874,6 +1883,31 @@ int compile_impl(const std::string& pattern, int engine, trre_prog** out, int mo
                 p->bt_ok = true;
             }
             make_guard(false);
+        } else if (mode == TRRE_MODE_SUB) {
+            // trre_sub_device_strings: the scan loop's nodes, built once, under two tables: this program keeps the markers' table of spans
+            // mode and carries the stack guard — its scan runs first —; an inner program, held as find mode holds its marks program, keeps
+            // the texts table of find mode (the marks table built with it is dropped).  Nothing else can run a sub program
+            const NftNodes nodes = build_nft_nodes(nft);
+            p->nft_nodes = (uint32_t)nodes.node.size();
+            p->gt = build_guided_spans(nodes);
+            std::unique_ptr<trre_prog> texts(new trre_prog);
+            GuidedTables marks_gt;
+            if (!p->gt.ok || !build_guided_find(nodes, texts->gt, marks_gt))
+                return fail(TRRE_E_UNSUPPORTED, "error: sub mode runs on the guided tables, and this pattern is beyond their limits (a backward automaton of more than 16 384 states)");
+            texts->engine = engine; texts->mode = TRRE_MODE_FIND;
+            texts->nft_states = p->nft_states; texts->nft_cons = p->nft_cons; texts->nft_nodes = p->nft_nodes;
+            texts->prints_newline = p->prints_newline;
+            serialize_stream(texts->gt.fwd, texts->gblob);
+            serialize_rev(texts->gt, texts->rblob);
+            {
+                GenTables lists;
+                lists.nodes = nodes;
+                lists.ok = true;
+                serialize_gen(lists, p->nblob);
+                p->bt_ok = true;
+            }
+            make_guard(false);
+            p->sub_texts = std::move(texts);
         } else {
             // TRRE_TRACE=1: the stages of the NFT compile on stderr as they start (to find the one a pattern is slow in)
             auto trace = [&](const char* what) { if (switches().trace) fprintf(stderr, "compile: %s\n", what); };
@@ -1962,6 +1996,7 @@ int trre_compile_mode(const uint8_t* pattern, size_t len, int engine, int mode, 
 void trre_free(trre_prog* p) {
     if (!p) return;
     trre_free(p->find_marks.release());
+    trre_free(p->sub_texts.release());
     int cur = 0;
     const bool have_cur = hipGetDevice(&cur) == hipSuccess;
     for (auto& kv : p->dev) {
@@ -2034,9 +2069,10 @@ size_t trre_export_stream_tables(const trre_prog* p, void* buf, size_t cap) { re
 
 size_t trre_export_guided_tables(const trre_prog* p, int which, void* buf, size_t cap) {
     if (!p) return 0;
+    if (which == 5 && p->sub_texts) return export_blob(p->sub_texts->gblob, buf, cap);      // (sub mode: the inner program's texts table)
     if (which == 5 || which == 6)                                     // (find mode: the texts / the marks forward tables; the backward DFA, 0, is one)
         return p->find_marks ? export_blob(which == 5 ? p->gblob : p->find_marks->gblob, buf, cap) : 0;
-    if (which == 7) return p->mode == TRRE_MODE_SPANS ? export_blob(p->gblob, buf, cap) : 0;     // (spans mode: the markers' forward table)
+    if (which == 7) return p->mode == TRRE_MODE_SPANS || p->mode == TRRE_MODE_SUB ? export_blob(p->gblob, buf, cap) : 0;     // (spans mode: the markers' forward table)
     if (which == 3 && p->find_marks) return export_blob(p->find_marks->kblob, buf, cap);     // (find mode: the guard goes with the scan that runs first)
     if (which == 4) return export_blob(p->gt.accept, buf, cap);       // (match mode: a byte per backward state, 1: a line that starts with the symbol is accepted)
     return export_blob(which == 0 ? p->rblob : (which == 2 ? p->nblob : (which == 3 ? p->kblob : p->gblob)), buf, cap);   // (2: the enumeration's / the backtracking fallback's tables, 3: the stack guard's)
@@ -2432,6 +2468,7 @@ static bool any_overlap(std::initializer_list<Range> have, std::initializer_list
 
 // the program of the span, split, filter and field calls; `noun`: what the refusing call makes
 static int spans_program(const trre_prog* p, const char* noun) {
+    if (p->mode == TRRE_MODE_SUB) return fail(TRRE_E_ARG, kSubOnlyMsg);
     if (p->mode != TRRE_MODE_SPANS || !p->gt.ok) return fail(TRRE_E_ARG, std::string("error: ") + noun + " take a program compiled with TRRE_MODE_SPANS");
     if (p->forced_family == TRRE_KERNEL_BACKTRACK)
         return fail(TRRE_E_UNSUPPORTED, "error: spans mode runs on the guided tables, which this program was told not to use (the backtracking family)");
@@ -2681,6 +2718,7 @@ int trre_match_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (out_len) *out_len = 0;
     if (n_matched) *n_matched = 0;
     if (!p || !d_off || !d_out_off || (n && !d_in) || (cap && !d_out) || (nrec && !d_valid)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_SUB) return fail(TRRE_E_ARG, kSubOnlyMsg);
     if (p->mode != TRRE_MODE_MATCH) return fail(TRRE_E_ARG, "error: matched strings take a program compiled with TRRE_MODE_MATCH");
     if (p->prints_newline)
         return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: record outputs could not be told apart");
@@ -2804,6 +2842,7 @@ int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     if (out_len) *out_len = 0;
     if (n_matches) *n_matches = 0;
     if (!p || !d_off || !d_list_off || (n && !d_in) || (cap && !d_out) || (match_cap && !d_match_off)) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_SUB) return fail(TRRE_E_ARG, kSubOnlyMsg);
     if (p->mode != TRRE_MODE_FIND || !p->find_marks) return fail(TRRE_E_ARG, "error: found strings take a program compiled with TRRE_MODE_FIND");
     if (p->prints_newline)
         return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: the matches' outputs could not be told apart");
@@ -3117,6 +3156,119 @@ int trre_field_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (const int rc = c.begin(p)) return rc;
     return field_on(p, c.st, d_in, n, d_off, nrec, k, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_valid, out_len,
                     static_cast<hipStream_t>(stream));
+}
+
+// ---- replaced strings (records_block.hpp) -----------------------------------------------------------------------------------
+// Steps 1 - 5 are the span call's, 6 its emit pass into the library's own arrays, 7 the find call's texts scan of the same staged
+// text under the inner program (stt: its state; its context holds the framed texts).  The outer context holds everything else.
+static int sub_on(trre_prog* p, DeviceState* st, DeviceState* stt, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t first,
+                  int64_t count, uint8_t* d_out, size_t cap, int64_t* d_out_off, size_t* n_replaced, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    SpanMarks mk;
+    int rc = span_marks(p, st, d_in, n, d_off, nrec, false, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 6. where every match starts and ends, and the list offsets: each array with its entry -1 in front
+    const size_t found = mk.found, slots = found + 2;
+    HIP_TRY(cx->d_sub_idx.reserve(slots, 4 * slots * 8));
+    HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
+    SubArgs a{};
+    a.in = d_in; a.n = (int64_t)n; a.off = d_off; a.nrec = (int64_t)nrec; a.L = cx->d_filter_lists;
+    a.S = cx->d_sub_idx + 1; a.E = a.S + slots; a.P = a.E + 2 * slots; a.found = (int64_t)found; a.first = first; a.count = count;
+    int64_t* xo = a.E + slots;
+    a.XO = xo;
+    SpanArgs& pa = mk.pa;
+    pa.start = a.S; pa.end = a.E; pa.list_off = cx->d_filter_lists; pa.n_match = (int64_t)found; pa.lists_only = 0u;
+    launch_span_emit(pa, s);
+    HIP_TRY(hipGetLastError());
+    // 7. the texts scan: every match's output and a '\n' — as many as there are matches; unframed into the library's own buffer
+    size_t m = 0;
+    const size_t total = n + nrec;
+    rc = find_scan(p->sub_texts.get(), stt, cx->d_snap, total, stt->ctx.d_framed, &m, s);
+    if (rc) return rc;                                      // (TRRE_E_DIVERGES: the caller's sizes stay 0)
+    const int64_t T = str_tile_bytes(), utiles = ((int64_t)m + T - 1) / T;
+    uint64_t closed = 0;
+    const uint64_t* before = nullptr;
+    if (m) {
+        rc = str_tile_newlines(cx, stt->ctx.d_framed, (int64_t)m, s, &before);
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+        if (rec_status(cx, s, const_cast<uint64_t*>(before) + utiles, &closed) < 0) return TRRE_E_DEVICE;
+    } else {
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (closed != found || m < found) return fail(TRRE_E_DEVICE, "error: the two scans of the strings disagree on the number of matches (internal)");
+    const size_t texts = m - found;
+    HIP_TRY(cx->d_sub_texts.reserve(texts + 64, texts + 64));
+    a.X = cx->d_sub_texts; a.x_len = (int64_t)texts;
+    if (found == 0) {
+        HIP_TRY(hipMemsetAsync(xo, 0, 8, s));
+    } else {
+        StrArgs ua{};
+        ua.src_v0 = stt->ctx.d_framed; ua.total = (int64_t)m; ua.dst = cx->d_sub_texts; ua.dst_len = (int64_t)texts;
+        ua.nrec = (int64_t)found; ua.out_off = xo;
+        ua.part = reinterpret_cast<const int64_t*>(before);
+        launch_find_unframe(ua, utiles, s);
+        HIP_TRY(hipGetLastError());
+    }
+    // 8. over chunks of matches: which are selected, and the selected matches, their texts' bytes and their matched bytes per chunk
+    //    and before it; the three totals and the status word in one read-back
+    const int64_t per = sub_chunk_matches();
+    a.chunks = std::max<int64_t>(((int64_t)found + per - 1) / per, 1);
+    HIP_TRY(cx->d_sub_cnt.reserve((size_t)a.chunks, (size_t)(6 * a.chunks + 4) * 8));
+    a.status = reinterpret_cast<uint32_t*>(cx->d_sub_cnt.p);
+    a.cnt = cx->d_sub_cnt + 1; a.base = a.cnt + 3 * a.chunks;
+    HIP_TRY(hipMemsetAsync(cx->d_sub_cnt, 0, 8, s));
+    launch_sub_plan(a, s);
+    uint64_t tot[3] = {0, 0, 0};
+    rc = scan_counts(a.cnt, a.base, 3, a.chunks, s, tot);
+    if (rc) return rc;
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, a.status, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad || tot[0] > found || tot[1] > texts || tot[2] > n) return fail(TRRE_E_DEVICE, "error: the replaced matches do not add up (internal)");
+    const size_t bytes = n - (size_t)tot[2] + (size_t)tot[1];
+    if (n_replaced) *n_replaced = (size_t)tot[0];
+    if (out_len) *out_len = bytes;
+    if (bytes > cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    // 9. where every segment starts; the output offsets; the splice (the size query may have no room for either)
+    if (d_out_off) {
+        a.out = d_out; a.out_len = (int64_t)bytes; a.out_off = d_out_off;
+        launch_sub_place(a, s);
+        launch_sub_offsets(a, s);
+        launch_sub_emit(a, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return TRRE_OK;
+}
+
+int trre_sub_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t first, int64_t count,
+                            uint8_t* d_out, size_t cap, int64_t* d_out_off, size_t* n_replaced, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_replaced) *n_replaced = 0;
+    if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (!d_out_off && (d_out || cap))) return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode != TRRE_MODE_SUB || !p->sub_texts) return fail(TRRE_E_ARG, "error: replaced strings take a program compiled with TRRE_MODE_SUB");
+    if (p->prints_newline)
+        return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: the matches' outputs could not be told apart");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: sub mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (first < 0) return fail(TRRE_E_ARG, "error: first must not be negative (count < 0 selects every match from first on)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    const size_t ob = (nrec + 1) * 8, pb = d_out_off ? ob : 0, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the replaced strings are not made in place)");
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_out_off, pb}}))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    ColumnCall c;
+    if (const int rc = c.begin(p, p->sub_texts.get())) return rc;
+    return sub_on(p, c.st, c.inner, d_in, n, d_off, nrec, first, count, d_out, cap, d_out_off, n_replaced, out_len, static_cast<hipStream_t>(stream));
 }
 
 namespace {

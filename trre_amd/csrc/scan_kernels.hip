@@ -1965,6 +1965,75 @@ __global__ __launch_bounds__(FG::THREADS) void k_field_emit(FieldArgs a) {
                      });
 }
 
+// ---- replaced strings (records_block.hpp; runtime.cpp: trre_sub_device_strings) --------------------------------------------
+// The selection bits and the chunk's three sums; a chunk out of order sets the status word.  No LDS but tile_totals' own.
+__global__ __launch_bounds__(FG::THREADS) void k_sub_plan(SubArgs a) {
+    uint64_t c[3];
+    uint32_t bad = sub_plan_thread<FG::THREADS>(a, blockIdx.x, threadIdx.x, c);
+    bad = wave_or(bad);
+    if ((threadIdx.x & (kWave - 1)) == 0 && bad) atomicOr(a.status, 1u);
+    tile_totals<uint64_t>(c, a.cnt, a.chunks, blockIdx.x);
+}
+
+// Where every segment starts.  The threads' sums of texts' and matched bytes are scanned over the workgroup in 64 bits: inside the
+// wave by shuffles of the two halves, across the waves through LDS, with the one barrier between the waves' totals and their readers.
+__device__ __forceinline__ uint64_t sub_wave_scan_incl(uint64_t v) {
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, kWave);
+        const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, kWave);
+        if (lane >= d) v += (uint64_t)hi << 32 | lo;
+    }
+    return v;
+}
+__global__ __launch_bounds__(FG::THREADS) void k_sub_place(SubArgs a) {
+    __shared__ uint64_t wtot[2][FG::THREADS / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    uint64_t c[3];
+    sub_place_sums<FG::THREADS>(a, blockIdx.x, tid, c);
+    const uint64_t it = sub_wave_scan_incl(c[1]), im = sub_wave_scan_incl(c[2]);
+    if (lane == kWave - 1) { wtot[0][w] = it; wtot[1][w] = im; }
+    __syncthreads();
+    uint64_t pt = it - c[1], pm = im - c[2];
+    for (int k = 0; k < w; ++k) { pt += wtot[0][k]; pm += wtot[1][k]; }
+    sub_place_thread<FG::THREADS>(a, blockIdx.x, tid, pt, pm);
+}
+
+__global__ __launch_bounds__(256) void k_sub_offsets(SubArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i <= a.nrec; i += stride) sub_offset(a, i);
+}
+
+// The splice.  Thread 0 finds the tile's window of segments; a barrier; all threads copy the window's places into LDS when they
+// fit (16 KiB, 16-byte aligned: static); a barrier; then the image and the window are only read.
+__global__ __launch_bounds__(FG::THREADS) void k_sub_emit(SubArgs a) {
+    __shared__ __attribute__((aligned(16))) int64_t image[kSubWindow];
+    __shared__ int64_t win[2];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const SubTile<FG> t(a, b);
+    if (tid == 0) sub_emit_window<FG>(a, t, win);
+    __syncthreads();
+    sub_keep_window<FG>(a, win, tid, image);
+    __syncthreads();
+    sub_emit_vecs<FG>(a, t, b, tid, win, image);
+}
+
+void launch_sub_plan(const SubArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_sub_plan, dim3((unsigned)a.chunks), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_sub_place(const SubArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_sub_place, dim3((unsigned)a.chunks), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_sub_offsets(const SubArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_sub_offsets, dim3(rec_grid(a.nrec + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_sub_emit(const SubArgs& a, void* stream) {
+    const int64_t A = (int64_t)(reinterpret_cast<uintptr_t>(a.out) & 15u), tiles = (A + a.out_len + FG::TILE - 1) / FG::TILE;
+    if (tiles > 0) hipLaunchKernelGGL(k_sub_emit, dim3((unsigned)tiles), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+int64_t sub_chunk_matches() { return (int64_t)FG::THREADS * kSubPer; }
+
 void launch_field_bounds(const SpanArgs& sp, const FieldArgs& a, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t groups = (a.f.nrec + kMatchThreads - 1) / kMatchThreads;
