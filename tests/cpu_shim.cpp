@@ -965,7 +965,7 @@ int shim_lazy_round(const uint8_t* cls, uint64_t* ent, const uint8_t* pool, uint
     miss[0] = 0;
     if (n == 0) return 0;
     // foreign_marks: every unexplored edge carries the mark of ANOTHER launch (a chunk in flight on the same table that listed it in ITS
-    // miss list, runtime.cpp: the host path's slots) — this launch must list the edges it needs all the same
+    // miss list, host_path.cpp: the host path's slots) — this launch must list the edges it needs all the same
     if (foreign_marks)
         for (size_t k = 0; k < ent_words; ++k)
             if (ent[k] == kLazyUnexplored) ent[k] = kLazyNoted | (uint64_t)0xdead << 32;
