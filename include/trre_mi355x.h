@@ -485,6 +485,49 @@ int trre_sub_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const i
                             int64_t count, uint8_t* d_out, size_t cap, int64_t* d_out_off, size_t* n_replaced, size_t* out_len,
                             void* stream);
 
+/* Match k of every string: the same column of strings under a program compiled with TRRE_MODE_FIND, and ONE of every string's
+ * matches taken — re.search(p, s).group(), s.str.extract(p), s.str.findall(p).str.get(k), SQL's regexp_extract(s, p) and
+ * regexp_substr(s, p, 1, k + 1), grep -o | head -1 per row — as a flat column with one entry per string and a validity bitmap.  The
+ * definition rests on trre_find_device_strings: string i has the list find(s_i) of c outputs o_0 .. o_{c-1} — the same attempts,
+ * cut at the first NUL, empty matches counted, an output that holds a NUL ending before it.  k >= 0 selects match k, k < 0 match
+ * c + k (-1: the last).  The string HAS the match exactly when that index lies in [0, c): then entry i is that output and the
+ * validity bit is set; otherwise the entry is empty and the bit is clear.  An empty output with the bit set is not an absent
+ * match ('x*' on "bb": k = 0, 1, 2 are valid and empty, k = 3 is absent; '[aie]:' on "kiwi": k = 0 is valid and empty).  Any k is
+ * legal: INT64_MIN selects nothing (k is compared, never negated).
+ *   d_out      cap bytes: the entries, concatenated in input order; *out_len is their total
+ *   d_out_off  nrec + 1 entries: entry i is d_out[d_out_off[i] .. d_out_off[i + 1]); d_out_off[0] = 0, d_out_off[nrec] = *out_len;
+ *              an absent entry has d_out_off[i + 1] == d_out_off[i]
+ *   d_valid    the Arrow validity bitmap, exactly as trre_field_device_strings defines it: 8 * ceil(nrec / 64) bytes, 8-byte
+ *              aligned (else TRRE_E_ARG), written as whole 64-bit words, bits at and beyond nrec zero
+ *   *n_valid   (may be null) the number of set bits;  *out_len may be null
+ * d_out may be null only with cap == 0, and d_out_off only when d_out is: that is the size query.  When no entry has bytes the
+ * call returns TRRE_OK and writes the offsets (all zero; if d_out_off is not null) and the bitmap.  nrec == 0 is valid with
+ * n == 0: TRRE_OK, and d_out_off[0] = 0 if d_out_off is not null.  The offsets' check (TRRE_E_ARG, nothing written), a string that
+ * holds a '\n' (TRRE_E_ARG, found on the device before anything of the caller's is written) and a split-form scan in flight: as
+ * for trre_find_device_strings.  Any overlap among d_in, d_off, d_out, d_out_off and d_valid: TRRE_E_ARG — there is no in-place
+ * form.  Refused before the device is touched, in this order: a null argument; a program compiled with TRRE_MODE_SUB (TRRE_E_ARG,
+ * with the message every call but trre_sub_device_strings gives it); any other program not compiled with TRRE_MODE_FIND
+ * (TRRE_E_ARG); a program that can print a '\n' of its own, TRRE_KERNEL_BACKTRACK forced through trre_set_kernel
+ * (TRRE_E_UNSUPPORTED); 2^55 strings or bytes, a misaligned bitmap, the overlaps (TRRE_E_ARG).
+ *   TRRE_E_CAPACITY  exactly when *out_len > cap: *out_len, *n_valid and d_valid are valid; d_out and d_out_off have not been
+ *                    written at all, and a retry with that room succeeds.
+ *   TRRE_E_DIVERGES  from either scan: *out_len = *n_valid = 0; the arrays are unspecified; trre_last_error() holds the message.
+ *   TRRE_E_DEVICE    the two scans disagree on the number of matches (internal), before anything of the caller's is written.
+ * How: the find call's two scans of the staged text — the marks scan, whose unframed offsets are the list offsets, and the texts
+ * scan — with everything they leave kept in arrays of the library's own: the list offsets, and the texts unframed with where each
+ * starts.  One pass over the strings, 64 to a wave, finds each string's match, writes the bitmap word by one ballot, parks where
+ * the entry starts in the texts, and leaves per chunk of 1 024 strings the strings with the match and the entries' bytes; two
+ * exclusive sums, whose totals are *n_valid and *out_len, read back in one synchronisation: the capacity decision.  A second pass
+ * over the strings stores d_out_off; and one output-driven pass writes d_out in 16 KiB tiles of its own address space as whole
+ * aligned 16-byte vectors, every vector's entry found by a binary search among the output offsets (the tile's window of them in
+ * LDS when it fits) — the unselected texts are never visited.  Every byte and word is stored once.
+ * Device memory, kept by the (prog, device) until trre_free: the find call's, the texts unframed (their bytes + 64), 8 bytes per
+ * match, 8 bytes per string and 32 bytes per 1 024 strings.  Synchronous with respect to `stream`; trre_last_scan_flags as for
+ * the find call. */
+int trre_nth_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k,
+                            uint8_t* d_out, size_t cap, int64_t* d_out_off, uint8_t* d_valid, size_t* n_valid, size_t* out_len,
+                            void* stream);
+
 /* What the last trre_scan_* call on the calling thread has to say beside its return code (thread-local, like trre_last_error;
  * trre_scan_finish adds to what its trre_scan_enqueue found). */
 #define TRRE_SCAN_GUARD_UNDECIDED 1u /* NFT engine: the input holds a line long enough to exhaust the reference's 65 536-item stack

@@ -104,6 +104,7 @@ def lib():
         L.trre_filter_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_field_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_sub_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_int64, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_nth_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
         L.trre_scan_finish.argtypes = [vp, ctypes.POINTER(sz)]
         L.trre_scan_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_int]
@@ -224,11 +225,11 @@ class Program:
     def __init__(self, pattern, engine="nft", mode="scan"):
         """mode "scan" (default), "match" (`trre -m`: whole-line matches only, NFT engine), "scan_all" (`trre -a`) or
         "match_all" (`trre -ma`): generator modes, every accepting path prints (NFT engine), or "find": every match of every
-        string as a list per string (find_strings / find_list, NFT engine), or "spans": where every match of every string starts
-        and ends (span_strings / span_list / count_strings, NFT engine) and the pieces between the matches (split_strings /
-        split_list), the strings with a match or without one (filter_strings / filter_list) and one piece of every string
-        (field_strings / field_list), or "sub": the first n matches of every string replaced by what they print (sub_strings /
-        sub_list, NFT engine)"""
+        string as a list per string (find_strings / find_list, NFT engine) and one match of every string (nth_strings /
+        nth_list), or "spans": where every match of every string starts and ends (span_strings / span_list / count_strings,
+        NFT engine) and the pieces between the matches (split_strings / split_list), the strings with a match or without one
+        (filter_strings / filter_list) and one piece of every string (field_strings / field_list), or "sub": the first n
+        matches of every string replaced by what they print (sub_strings / sub_list, NFT engine)"""
         self.pattern = _bytes(pattern)
         self.engine = _ENGINES[engine]
         self.mode = {"scan": MODE_SCAN, "match": MODE_MATCH, "scan_all": MODE_SCAN_ALL, "match_all": MODE_MATCH_ALL,
@@ -420,6 +421,37 @@ class Program:
         """list of bytes in -> list of lists of bytes out: every match's output, string by string (through find_strings)"""
         recs, off, values, offsets = _pack(records, device)
         return _read_back(*self.find_strings(values, offsets))
+
+    def nth_strings(self, values, offsets, k=0, stream=None, packed=False):
+        """Match k of every string (trre_nth_device_strings; a program compiled with mode="find"): values and offsets as for
+        scan_strings, no string holding a b"\\n".  ONE entry of every string's list of find_strings: match k, or, for k < 0,
+        match k counted from the end (-1: the last), as re.search(p, s).group() (k = 0), s.str.findall(p).str.get(k) and SQL's
+        regexp_substr(s, p, 1, k + 1).  Returns (out, out_offsets, valid): string i's entry is
+        out[out_offsets[i]:out_offsets[i + 1]], empty when the string has no such match, and valid[i] says whether it has (an
+        empty output of a match that exists is valid).  valid is a torch.bool tensor of nrec entries; with packed=True it is the
+        Arrow validity bitmap as the library wrote it (uint8, 8 * ceil(nrec / 64) bytes, bit i & 7 of byte i >> 3).  Two calls:
+        the size query, then the one that fills a buffer of exactly that size."""
+        import torch
+        n, nrec, s = _column(values, offsets, stream)
+        words = torch.zeros(max((nrec + 63) // 64, 1), dtype=torch.int64, device=values.device)     # (8-byte aligned)
+        m, v = ctypes.c_size_t(), ctypes.c_size_t()
+
+        def call(o, cap, oo):
+            return lib().trre_nth_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, k, o, cap, oo,
+                                                 words.data_ptr(), ctypes.byref(v), ctypes.byref(m), s)
+
+        def alloc(v, m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
+            out_off = torch.zeros(nrec + 1, dtype=torch.int64, device=values.device)     # (no entry has bytes: all zero, as they are)
+            return (out[:m], out_off), (out.data_ptr(), m, out_off.data_ptr())
+        return _query_then_fill(call, (None, 0, None), alloc, (v, m), values.device) + (_validity(words, nrec, packed),)
+
+    def nth_list(self, records, k=0, device=0):
+        """list of bytes in -> list out: the output of match k of every string (bytes), None where the string has no such match
+        (through nth_strings)"""
+        recs, off, values, offsets = _pack(records, device)
+        out, out_off, valid = self.nth_strings(values, offsets, k)
+        return [b if ok else None for b, ok in zip(_read_back(out, out_off), valid.cpu().numpy().tolist())]
 
     def _span_call(self, values, offsets, stream):
         """trre_span_device_strings on a column: (call(d_start, d_end, span_cap) -> rc, *n_matches, list_offsets)"""

@@ -443,23 +443,54 @@ static int find_scan(trre_prog* p, DeviceState* st, const uint8_t* d_text, size_
     }
 }
 
+// The texts scan of the staged text (cx->d_snap, `total` bytes) under the program `texts` (stt: its state) into `framed`: every match's
+// output and a '\n' — as many as `found`, the matches the other scan counted.  *m: the framed texts' bytes; *before [tiles + 1]: the
+// '\n' before every string tile (16 KiB) of them, in a fresh carve of cx; their total is read back and checked.  What the find and
+// nth calls' step 5 and the sub call's step 7 share.
+static int find_texts(trre_prog* texts, DeviceState* stt, ScanCtx* cx, size_t total, DevBuf<uint8_t>& framed, size_t found, hipStream_t s,
+                      size_t* m, const uint64_t** before) {
+    int rc = find_scan(texts, stt, cx->d_snap, total, framed, m, s);
+    if (rc) return rc;                                      // (TRRE_E_DIVERGES: the caller's sizes stay 0)
+    const int64_t T = trre::str_tile_bytes(), utiles = ((int64_t)*m + T - 1) / T;
+    uint64_t closed = 0;
+    *before = nullptr;
+    if (*m) {
+        rc = str_tile_newlines(cx, framed, (int64_t)*m, s, before);
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+        if (rec_status(cx, s, const_cast<uint64_t*>(*before) + utiles, &closed) < 0) return TRRE_E_DEVICE;
+    } else {
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (closed != found || *m < found) return fail(TRRE_E_DEVICE, "error: the two scans of the strings disagree on the number of matches (internal)");
+    return TRRE_OK;
+}
+
 // d_rec as for the strings call, of the outer program's context, which also holds the staged text (d_snap), the list offsets while
-// they are being made (d_find_off), the marks unframed (d_find_marks) and the framed texts (d_framed); the inner program's context
-// holds the framed marks (its d_framed)
-static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec,
-                   uint8_t* d_out, size_t cap, int64_t* d_match_off, size_t match_cap, int64_t* d_list_off, size_t* n_matches,
-                   size_t* out_len, hipStream_t s) {
+// they are being made and after (d_find_off), the marks unframed (d_find_marks) and the framed texts (d_framed); the inner program's
+// context holds the framed marks (its d_framed)
+struct FoundTexts {
+    bool empty;             // nrec == 0: the offsets passed and nothing else ran
+    size_t found;           // matches
+    size_t m;               // the framed texts' bytes: the texts' and a '\n' per match
+    const uint64_t* before; // [tiles + 1] '\n' before every string tile of the framed texts (null: m == 0)
+};
+
+// What the find call and the nth call share, steps 1 - 5: the offsets' check, the staged text, its newline check, the marks scan
+// with the list offsets L into cx->d_find_off, the texts scan into cx->d_framed with the closed-count check.  d_list_off (the find
+// call; null: the nth call): L is copied there as soon as it is made, behind the strings' check and before the texts scan.
+static int find_marks_texts(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec,
+                            int64_t* d_list_off, hipStream_t s, FoundTexts* out) {
     using namespace trre;
     ScanCtx* cx = &st->ctx;
     const int64_t T = str_tile_bytes();
     const int64_t total = (int64_t)(n + nrec);                     // the staged text
+    *out = FoundTexts{};
     // 1. the offsets, on the device: nothing is written before they pass
     int rc = rec_check_offsets(cx, (total + T - 1) / T, d_off, nrec, n, s);
     if (rc) return rc;
     if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
-        if (d_match_off) HIP_TRY(hipMemsetAsync(d_match_off, 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        out->empty = true;
         return TRRE_OK;
     }
     // 2. the staged text and the strings' ranks, as for the strings call — the ranks into the library's own array: the caller's
@@ -490,23 +521,27 @@ static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_
     if (lost || last != mm || marks_nl != nrec) return fail(TRRE_E_DEVICE, "error: the list offsets do not add up (internal)");
     rc = str_unframe_located(cx, marks, (int64_t)mm, cx->d_find_marks, nrec, loff, s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(d_list_off, loff, (nrec + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (d_list_off) HIP_TRY(hipMemcpyAsync(d_list_off, loff, (nrec + 1) * 8, hipMemcpyDeviceToDevice, s));
     // 5. the texts scan: every match's output and a '\n' — as many as there are marks
-    size_t m = 0;
-    rc = find_scan(p, st, cx->d_snap, (size_t)total, cx->d_framed, &m, s);
+    out->found = found;
+    return find_texts(p, st, cx, (size_t)total, cx->d_framed, found, s, &out->m, &out->before);
+}
+
+static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec,
+                   uint8_t* d_out, size_t cap, int64_t* d_match_off, size_t match_cap, int64_t* d_list_off, size_t* n_matches,
+                   size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    FoundTexts ft;
+    const int rc = find_marks_texts(p, st, stm, d_in, n, d_off, nrec, d_list_off, s, &ft);
     if (rc) return rc;
-    const int64_t utiles = ((int64_t)m + T - 1) / T;
-    uint64_t closed = 0;
-    const uint64_t* before = nullptr;                       // '\n' before every tile of the texts
-    if (m) {
-        rc = str_tile_newlines(cx, cx->d_framed, (int64_t)m, s, &before);
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        if (rec_status(cx, s, const_cast<uint64_t*>(before) + utiles, &closed) < 0) return TRRE_E_DEVICE;
-    } else {
+    if (ft.empty) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
+        if (d_match_off) HIP_TRY(hipMemsetAsync(d_match_off, 0, 8, s));
         HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
     }
-    if (closed != found || m < found) return fail(TRRE_E_DEVICE, "error: the two scans of the strings disagree on the number of matches (internal)");
+    const size_t found = ft.found, m = ft.m;
     if (n_matches) *n_matches = found;
     if (out_len) *out_len = m - found;
     if (m - found > cap || found > match_cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
@@ -514,11 +549,12 @@ static int find_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_
     if (found == 0) {
         if (d_match_off) HIP_TRY(hipMemsetAsync(d_match_off, 0, 8, s));
     } else {
+        const int64_t T = str_tile_bytes();
         StrArgs ua{};
         ua.src_v0 = cx->d_framed; ua.total = (int64_t)m; ua.dst = d_out; ua.dst_len = (int64_t)(m - found);
         ua.nrec = (int64_t)found; ua.out_off = d_match_off;
-        ua.part = reinterpret_cast<const int64_t*>(before);
-        launch_find_unframe(ua, utiles, s);
+        ua.part = reinterpret_cast<const int64_t*>(ft.before);
+        launch_find_unframe(ua, ((int64_t)m + T - 1) / T, s);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s));
@@ -545,6 +581,100 @@ int trre_find_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const 
     ColumnCall c;
     if (const int rc = c.begin(p, p->find_marks.get())) return rc;
     return find_on(p, c.st, c.inner, d_in, n, d_off, nrec, d_out, cap, d_match_off, match_cap, d_list_off, n_matches, out_len, static_cast<hipStream_t>(stream));
+}
+
+// ---- match k of every string (records_block.hpp) ---------------------------------------------------------------------------
+// Steps 1 - 5 are the find call's.  The outer context also holds the texts unframed (d_nth_texts) with their offsets (d_nth_xo), the
+// entries' sources (d_nth_src) and the plan's status word, counts and bases (d_nth_cnt).
+static int nth_on(trre_prog* p, DeviceState* st, DeviceState* stm, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k,
+                  uint8_t* d_out, size_t cap, int64_t* d_out_off, uint64_t* d_valid, size_t* n_valid, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    FoundTexts ft;
+    int rc = find_marks_texts(p, st, stm, d_in, n, d_off, nrec, nullptr, s, &ft);
+    if (rc) return rc;
+    if (ft.empty) {
+        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 6. the framed texts without their newlines into the library's own buffer, and where each match's text starts
+    const size_t found = ft.found, texts = ft.m - found;
+    HIP_TRY(cx->d_nth_xo.reserve(found + 1, (found + 1) * 8));
+    HIP_TRY(cx->d_nth_texts.reserve(texts + 64, texts + 64));
+    if (found == 0) {
+        HIP_TRY(hipMemsetAsync(cx->d_nth_xo, 0, 8, s));
+    } else {
+        const int64_t T = str_tile_bytes();
+        StrArgs ua{};
+        ua.src_v0 = cx->d_framed; ua.total = (int64_t)ft.m; ua.dst = cx->d_nth_texts; ua.dst_len = (int64_t)texts;
+        ua.nrec = (int64_t)found; ua.out_off = cx->d_nth_xo;
+        ua.part = reinterpret_cast<const int64_t*>(ft.before);
+        launch_find_unframe(ua, ((int64_t)ft.m + T - 1) / T, s);
+        HIP_TRY(hipGetLastError());
+    }
+    // 7. over chunks of strings: the bitmap, where every entry starts in the texts, and the strings with the match and the entries'
+    //    bytes per chunk and before it; the two totals and the status word in one read-back
+    const int64_t per = nth_chunk_strings();
+    NthArgs a{};
+    a.L = cx->d_find_off; a.nrec = (int64_t)nrec; a.XO = cx->d_nth_xo; a.X = cx->d_nth_texts; a.x_len = (int64_t)texts; a.found = (int64_t)found;
+    a.k = k; a.valid = d_valid; a.words = (int64_t)((nrec + 63) / 64);
+    a.chunks = ((int64_t)nrec + per - 1) / per;
+    HIP_TRY(cx->d_nth_src.reserve(nrec, nrec * 8));
+    HIP_TRY(cx->d_nth_cnt.reserve((size_t)a.chunks, (size_t)(4 * a.chunks + 3) * 8));
+    a.src = cx->d_nth_src;
+    a.status = reinterpret_cast<uint32_t*>(cx->d_nth_cnt.p);
+    a.cnt = cx->d_nth_cnt + 1; a.base = a.cnt + 2 * a.chunks;
+    HIP_TRY(hipMemsetAsync(cx->d_nth_cnt, 0, 8, s));
+    launch_nth_plan(a, s);
+    uint64_t tot[2] = {0, 0};
+    rc = scan_counts(a.cnt, a.base, 2, a.chunks, s, tot);
+    if (rc) return rc;
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, a.status, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad || tot[0] > nrec || tot[1] > texts) return fail(TRRE_E_DEVICE, "error: the selected matches do not add up (internal)");
+    const size_t bytes = (size_t)tot[1];
+    if (n_valid) *n_valid = (size_t)tot[0];
+    if (out_len) *out_len = bytes;
+    if (bytes > cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    // 8. where every entry starts; the entries' bytes (the size query may have no room for either)
+    if (d_out_off) {
+        a.out = d_out; a.out_len = (int64_t)bytes; a.out_off = d_out_off;
+        launch_nth_offsets(a, s);
+        launch_nth_emit(a, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return TRRE_OK;
+}
+
+int trre_nth_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k, uint8_t* d_out, size_t cap,
+                            int64_t* d_out_off, uint8_t* d_valid, size_t* n_valid, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_valid) *n_valid = 0;
+    if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (!d_out_off && (d_out || cap)) || (nrec && !d_valid))
+        return fail(TRRE_E_ARG, "error: null argument");
+    if (p->mode == TRRE_MODE_SUB) return fail(TRRE_E_ARG, kSubOnlyMsg);
+    if (p->mode != TRRE_MODE_FIND || !p->find_marks) return fail(TRRE_E_ARG, "error: match k of every string takes a program compiled with TRRE_MODE_FIND");
+    if (p->prints_newline)
+        return fail(TRRE_E_UNSUPPORTED, "error: the pattern can print a newline of its own: the matches' outputs could not be told apart");
+    if (p->forced_family == TRRE_KERNEL_BACKTRACK)
+        return fail(TRRE_E_UNSUPPORTED, "error: find mode runs on the guided tables, which this program was told not to use (the backtracking family)");
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    if (reinterpret_cast<uintptr_t>(d_valid) & 7u) return fail(TRRE_E_ARG, "error: the validity bitmap must be 8-byte aligned (it is written as 64-bit words)");
+    const size_t ob = (nrec + 1) * 8, pb = d_out_off ? ob : 0, vb = (nrec + 63) / 64 * 8, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the selected matches are not made in place)");
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_out_off, pb}}))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    if (any_overlap({{d_in, n}, {d_out, cb}, {d_off, ob}, {d_out_off, pb}}, {{d_valid, vb}}))
+        return fail(TRRE_E_ARG, "error: the validity bitmap overlaps the data or an offsets array");
+    ColumnCall c;
+    if (const int rc = c.begin(p, p->find_marks.get())) return rc;
+    return nth_on(p, c.st, c.inner, d_in, n, d_off, nrec, k, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_valid, out_len,
+                  static_cast<hipStream_t>(stream));
 }
 
 // ---- match spans and split strings (records_block.hpp) ---------------------------------------------------------------------
@@ -878,20 +1008,10 @@ static int sub_on(trre_prog* p, DeviceState* st, DeviceState* stt, const uint8_t
     // 7. the texts scan: every match's output and a '\n' — as many as there are matches; unframed into the library's own buffer
     size_t m = 0;
     const size_t total = n + nrec;
-    rc = find_scan(p->sub_texts.get(), stt, cx->d_snap, total, stt->ctx.d_framed, &m, s);
+    const uint64_t* before = nullptr;
+    rc = find_texts(p->sub_texts.get(), stt, cx, total, stt->ctx.d_framed, found, s, &m, &before);
     if (rc) return rc;                                      // (TRRE_E_DIVERGES: the caller's sizes stay 0)
     const int64_t T = str_tile_bytes(), utiles = ((int64_t)m + T - 1) / T;
-    uint64_t closed = 0;
-    const uint64_t* before = nullptr;
-    if (m) {
-        rc = str_tile_newlines(cx, stt->ctx.d_framed, (int64_t)m, s, &before);
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        if (rec_status(cx, s, const_cast<uint64_t*>(before) + utiles, &closed) < 0) return TRRE_E_DEVICE;
-    } else {
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (closed != found || m < found) return fail(TRRE_E_DEVICE, "error: the two scans of the strings disagree on the number of matches (internal)");
     const size_t texts = m - found;
     HIP_TRY(cx->d_sub_texts.reserve(texts + 64, texts + 64));
     a.X = cx->d_sub_texts; a.x_len = (int64_t)texts;

@@ -19,6 +19,7 @@ struct SplitArgs;
 struct FilterArgs;
 struct FieldArgs;
 struct SubArgs;
+struct NthArgs;
 
 constexpr int kEngineNft = 0, kEngineDft = 1;
 
@@ -141,6 +142,14 @@ void launch_sub_plan(const SubArgs& a, void* stream);
 void launch_sub_place(const SubArgs& a, void* stream);
 void launch_sub_offsets(const SubArgs& a, void* stream);
 void launch_sub_emit(const SubArgs& a, void* stream);
+// match k of every string (records_block.hpp), behind the find call's list offsets and launch_find_unframe's texts: the bitmap, the
+// entries' sources and the strings with the match and the entries' bytes per chunk of nth_chunk_strings() strings (a.cnt; a.status
+// |= 1 when the arrays are out of order); then — behind their two exclusive scans — the output offsets; the entries' bytes
+// (nothing is launched for an empty output)
+int64_t nth_chunk_strings();
+void launch_nth_plan(const NthArgs& a, void* stream);
+void launch_nth_offsets(const NthArgs& a, void* stream);
+void launch_nth_emit(const NthArgs& a, void* stream);
 void launch_bytemap_shift(const uint8_t* blob, const uint8_t* src, uint8_t* dst, int64_t len, bool nl, void* stream);
 
 }  // namespace trre

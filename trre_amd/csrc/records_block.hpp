@@ -1409,4 +1409,165 @@ TRRE_HD void sub_emit_vecs(const SubArgs& a, const SubTile<G>& t, int64_t b, int
     }
 }
 
+// ---- match k of every string (trre_nth_device_strings) ---------------------------------------------------------------------
+// One entry per string of the find call's lists: with c_i = L[i + 1] - L[i] the string's matches, entry i is match
+// j_i = L[i] + kk_i of the column, kk_i = k (k >= 0) or c_i + k (k < 0); the string HAS the match exactly when kk_i lies in
+// [0, c_i).  The find call's two scans leave the list offsets L[nrec + 1] and, unframed, the texts X with XO[found + 1], in
+// arrays of the library's own.  Entry i is X[src_i, src_i + len_i), src_i = XO[j_i], len_i = XO[j_i + 1] - XO[j_i], both 0 when
+// the match is absent: the sources are ordered but NOT adjacent, so the passes are string-driven up to the sizes and
+// output-driven for the bytes — no compaction over all the texts.  Over CHUNKS of THREADS * kNthPer consecutive strings:
+//   k_nth_plan     string (c * kNthPer + r) * THREADS + tid in round r: 64 consecutive strings to a wave, so the wave's verdicts
+//                  are one ballot, the bitmap word; src_i parked; cnt[2][chunks]: the strings with the match and the entries'
+//                  bytes; and the check that L and the texts' offsets are ordered and in range (a status word)
+//   k_chunk_scan   twice: base[2][chunks + 1]; the totals are n_valid and out_len: the capacity decision
+//   k_nth_offsets  a thread has kNthPer strings in a row: out_off[i + 1] from the chunk's base and a workgroup scan of the
+//                  threads' sums of len_i
+//   k_nth_emit     k_sub_emit with one source: output-driven over tiles of TILE bytes of the OUTPUT's v-space (v = position + the
+//                  address of out mod 16).  Thread 0 finds the entries the tile touches by two binary searches in out_off (the
+//                  LAST entry that starts at or before a position: behind a run of empty entries at one position that is the one
+//                  with the bytes, found by one search); when that window of out_off fits, all threads copy it into LDS (kSubWindow
+//                  entries, 16 KiB: k_sub_emit's budget, which leaves the CU's residency to the registers); then a thread
+//                  owns destination vectors j * THREADS + tid.  A whole vector inside one entry is one unaligned 16-byte read (two
+//                  aligned loads and a funnel shift) and one aligned 16-byte store; any other is put together piece by piece.
+// Who writes which byte and word: every bitmap word lane 0 of its wave in k_nth_plan (lanes at or beyond nrec vote false: the
+// tail is zero); src_i the thread that owns string i there; out_off[0] thread 0 of chunk 0 in k_nth_offsets, out_off[i + 1] the
+// thread that owns string i; every output byte the thread that owns its destination vector, once; the ragged first and last
+// vectors of the buffer are byte stores, and nothing at or behind out_len is stored.
+constexpr int kNthPer = 4;                            // strings per thread: chunks of 1 024
+
+struct NthArgs {
+    const int64_t* L;       // [nrec + 1] the find call's list offsets
+    int64_t nrec;
+    const int64_t* XO;      // [found + 1] the texts' offsets (k_find_unframe)
+    const uint8_t* X;       // the texts
+    int64_t x_len;          // their bytes: XO[found]
+    int64_t found;
+    int64_t k;              // which match
+    int64_t* src;           // [nrec] where entry i starts in X
+    uint64_t* valid;        // [words] the bitmap
+    int64_t words;          // ceil(nrec / 64)
+    int64_t chunks;
+    uint64_t* cnt;          // [2][chunks] strings with the match, the entries' bytes
+    const uint64_t* base;   // [2][chunks + 1] their exclusive scans
+    uint32_t* status;       // |= 1: the list offsets or the texts' offsets are not ordered (internal)
+    uint8_t* out;           // [out_len]
+    int64_t out_len;
+    int64_t* out_off;       // [nrec + 1]
+};
+
+// the match k selects in string i, as its number j in the column; true when the string has it.  (c >= 0 > k: the sum cannot
+// overflow, k is never negated, and L[i] + kk is formed only where kk < c)
+TRRE_HD bool nth_index(const NthArgs& a, int64_t i, int64_t& j) {
+    const int64_t l0 = a.L[i], c = a.L[i + 1] - l0;
+    const int64_t kk = a.k >= 0 ? a.k : c + a.k;
+    if (kk < 0 || kk >= c) return false;
+    j = l0 + kk;
+    return true;
+}
+// k_nth_plan: the string of thread tid in round r of chunk c
+template <int THREADS>
+TRRE_HD int64_t nth_plan_string(int64_t c, int r, int tid) { return (c * kNthPer + r) * THREADS + tid; }
+// ... its verdict; src_i parked; c2 += (1, len_i) when it has the match; bad |= 1 when an array is out of order (the string
+// then counts as without the match)
+TRRE_HD bool nth_plan(const NthArgs& a, int64_t i, uint64_t (&c2)[2], uint32_t& bad) {
+    const int64_t l0 = a.L[i], l1 = a.L[i + 1];
+    int64_t j, x0 = 0, x1 = 0;
+    bool has = false;
+    if (l0 < 0 || l0 > l1 || l1 > a.found) {
+        bad = 1;
+    } else if (nth_index(a, i, j)) {
+        x0 = a.XO[j]; x1 = a.XO[j + 1];
+        has = x0 >= 0 && x0 <= x1 && x1 <= a.x_len;
+        if (!has) bad = 1;
+    }
+    a.src[i] = has ? x0 : 0;
+    if (has) { c2[0] += 1; c2[1] += (uint64_t)(x1 - x0); }
+    return has;
+}
+TRRE_HD int64_t nth_len(const NthArgs& a, int64_t i) {
+    int64_t j;
+    return nth_index(a, i, j) ? a.XO[j + 1] - a.XO[j] : 0;
+}
+// k_nth_offsets: the bytes of the thread's kNthPer strings of chunk c
+template <int THREADS>
+TRRE_HD uint64_t nth_offsets_sum(const NthArgs& a, int64_t c, int tid) {
+    uint64_t s = 0;
+    const int64_t i0 = (c * THREADS + tid) * kNthPer;
+    for (int64_t i = i0; i < i0 + kNthPer && i < a.nrec; ++i) s += (uint64_t)nth_len(a, i);
+    return s;
+}
+// ... and their offsets; pre: the bytes of the chunk before the thread's strings
+template <int THREADS>
+TRRE_HD void nth_offsets_thread(const NthArgs& a, int64_t c, int tid, uint64_t pre) {
+    int64_t o = (int64_t)(a.base[a.chunks + 1 + c] + pre);
+    const int64_t i0 = (c * THREADS + tid) * kNthPer;
+    if (i0 == 0) a.out_off[0] = 0;
+    for (int64_t i = i0; i < i0 + kNthPer && i < a.nrec; ++i) {
+        o += nth_len(a, i);
+        a.out_off[i + 1] = o;
+    }
+}
+
+// k_nth_emit
+template <class G>
+struct NthTile {
+    int A;                  // the address of out mod 16
+    int64_t o0, o1;         // the tile's output positions
+    TRRE_HD NthTile(const NthArgs& a, int64_t b) {
+        A = (int)(reinterpret_cast<uintptr_t>(a.out) & 15u);
+        o0 = b * G::TILE - A > 0 ? b * G::TILE - A : 0;
+        o1 = (b + 1) * G::TILE - A < a.out_len ? (b + 1) * G::TILE - A : a.out_len;
+    }
+};
+// thread 0: the entries [win[0], win[1]] the tile touches — the entry that holds output position o (o < out_len) is the last i
+// with out_off[i] <= o (out_off[0] = 0 <= o < out_len = out_off[nrec]: 0 <= i < nrec, and it has bytes)
+template <class G>
+TRRE_HD void nth_emit_window(const NthArgs& a, const NthTile<G>& t, int64_t* win) {
+    win[0] = rec_lower_bound(SubPlaceKey{a.out_off}, a.nrec + 1, t.o0 + 1) - 1;
+    win[1] = rec_lower_bound(SubPlaceKey{a.out_off}, a.nrec + 1, t.o1) - 1;
+}
+// all threads: out_off[win[0] .. win[1] + 1] into the image, when it fits
+template <class G>
+TRRE_HD void nth_keep_window(const NthArgs& a, const int64_t* win, int tid, int64_t* image) {
+    const int64_t cnt = win[1] - win[0] + 2;
+    if (cnt > kSubWindow) return;
+    for (int64_t k = tid; k < cnt; k += G::THREADS) image[k] = a.out_off[win[0] + k];
+}
+// the thread's destination vectors of tile b
+template <class G>
+TRRE_HD void nth_emit_vecs(const NthArgs& a, const NthTile<G>& t, int64_t b, int tid, const int64_t* win, const int64_t* image) {
+    const int64_t wcnt = win[1] - win[0] + 2;
+    const SubPlaces pz{a.out_off, image, win[0], wcnt > kSubWindow ? 0 : wcnt};
+    for (int j = 0; j < G::VECS; ++j) {
+        const int64_t v = b * G::TILE + 16 * ((int64_t)j * G::THREADS + tid);
+        const int64_t p0 = v - t.A > 0 ? v - t.A : 0, p1 = v + 16 - t.A < a.out_len ? v + 16 - t.A : a.out_len;
+        if (p1 <= p0) continue;
+        const int cnt = (int)(p1 - p0);
+        int64_t i = sub_segment_in(pz, win[0], win[1], p0);
+        int64_t beg = pz(i), end = pz(i + 1);
+        uint8_t* d = a.out + p0;
+        if (cnt == 16 && p0 + 16 <= end) {
+            rec_store16(d, sub_load16u(a.X + a.src[i] + (p0 - beg)));
+            continue;
+        }
+        U128 r;
+        r.x = r.y = r.z = r.w = 0;
+        int64_t o = p0;
+        for (int f = 0;;) {
+            const int take = end - o < cnt - f ? (int)(end - o) : cnt - f;
+            const uint8_t* x = a.X + a.src[i] + (o - beg);
+            for (int q = 0; q < take; ++q) str_put_byte(r, f + q, x[q]);
+            f += take; o += take;
+            if (f >= cnt) break;
+            i = pz(i + 2) > o ? i + 1 : sub_segment_in(pz, i + 1, win[1], o);      // (o < out_len: entry i + 1 exists)
+            beg = pz(i); end = pz(i + 1);
+        }
+        if (cnt == 16) {
+            rec_store16(d, r);
+        } else {
+            for (int q = 0; q < cnt; ++q) d[q] = (uint8_t)filter_get_byte(r, q);
+        }
+    }
+}
+
 }  // namespace trre

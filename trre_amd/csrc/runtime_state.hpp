@@ -107,6 +107,10 @@ struct ScanCtx {
     DevBuf<int64_t> d_sub_idx;        // trre_sub_device_strings: S, E, XO, P, each [found + 2] with entry -1 in front (matches)
     DevBuf<uint8_t> d_sub_texts;      // ... the texts scan unframed (bytes)
     DevBuf<uint64_t> d_sub_cnt;       // ... the status word, cnt [3][chunks], base [3][chunks + 1] (chunks)
+    DevBuf<int64_t> d_nth_xo;         // trre_nth_device_strings: the texts' offsets XO [found + 1] (matches)
+    DevBuf<uint8_t> d_nth_texts;      // ... the texts scan unframed (bytes)
+    DevBuf<int64_t> d_nth_src;        // ... where every entry starts in the texts [nrec] (strings)
+    DevBuf<uint64_t> d_nth_cnt;       // ... the status word, cnt [2][chunks], base [2][chunks + 1] (chunks)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the copy form of a large table (scan_block.hpp fb_lane<3> / fb_copy_lane): events, lane headers (rows of kCopyEvCap events)
     DevBuf<uint32_t> d_cevents, d_chdr;

@@ -2019,6 +2019,67 @@ __global__ __launch_bounds__(FG::THREADS) void k_sub_emit(SubArgs a) {
     sub_emit_vecs<FG>(a, t, b, tid, win, image);
 }
 
+// ---- match k of every string (records_block.hpp; column_calls.cpp: trre_nth_device_strings) --------------------------------
+// The verdicts, the parked sources and the chunk's two sums.  Every thread runs every round (the ballot is the wave's bitmap word:
+// the 64 strings of a wave in a round are consecutive and start at a multiple of 64); lanes at or beyond nrec vote false.  No LDS
+// but tile_totals' own.
+__global__ __launch_bounds__(FG::THREADS) void k_nth_plan(NthArgs a) {
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    uint64_t c[2] = {0, 0};
+    uint32_t bad = 0;
+    for (int r = 0; r < kNthPer; ++r) {
+        const int64_t i = nth_plan_string<FG::THREADS>(blockIdx.x, r, tid);
+        const bool has = i < a.nrec && nth_plan(a, i, c, bad);
+        const uint64_t word = __ballot(has);
+        const int64_t at = i / kWave;
+        if (lane == 0 && at < a.words) a.valid[at] = word;
+    }
+    bad = wave_or(bad);
+    if (lane == 0 && bad) atomicOr(a.status, 1u);
+    tile_totals<uint64_t>(c, a.cnt, a.chunks, blockIdx.x);
+}
+
+// Where every entry starts: the threads' bytes scanned over the workgroup in 64 bits, as k_sub_place scans its sums — inside the
+// wave by shuffles, across the waves through LDS, with the one barrier between the waves' totals and their readers.
+__global__ __launch_bounds__(FG::THREADS) void k_nth_offsets(NthArgs a) {
+    __shared__ uint64_t wtot[FG::THREADS / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    const uint64_t mine = nth_offsets_sum<FG::THREADS>(a, blockIdx.x, tid);
+    const uint64_t inc = sub_wave_scan_incl(mine);
+    if (lane == kWave - 1) wtot[w] = inc;
+    __syncthreads();
+    uint64_t pre = inc - mine;
+    for (int k = 0; k < w; ++k) pre += wtot[k];
+    nth_offsets_thread<FG::THREADS>(a, blockIdx.x, tid, pre);
+}
+
+// The entries' bytes.  Thread 0 finds the tile's window of entries; a barrier; all threads copy the window's offsets into LDS when
+// they fit (16 KiB, 16-byte aligned: static); a barrier; then the image and the window are only read.
+__global__ __launch_bounds__(FG::THREADS) void k_nth_emit(NthArgs a) {
+    __shared__ __attribute__((aligned(16))) int64_t image[kSubWindow];
+    __shared__ int64_t win[2];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const NthTile<FG> t(a, b);
+    if (tid == 0) nth_emit_window<FG>(a, t, win);
+    __syncthreads();
+    nth_keep_window<FG>(a, win, tid, image);
+    __syncthreads();
+    nth_emit_vecs<FG>(a, t, b, tid, win, image);
+}
+
+int64_t nth_chunk_strings() { return (int64_t)FG::THREADS * kNthPer; }
+void launch_nth_plan(const NthArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_nth_plan, dim3((unsigned)a.chunks), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_nth_offsets(const NthArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_nth_offsets, dim3((unsigned)a.chunks), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_nth_emit(const NthArgs& a, void* stream) {
+    const int64_t A = (int64_t)(reinterpret_cast<uintptr_t>(a.out) & 15u), tiles = a.out_len ? (A + a.out_len + FG::TILE - 1) / FG::TILE : 0;
+    if (tiles > 0) hipLaunchKernelGGL(k_nth_emit, dim3((unsigned)tiles), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+
 void launch_sub_plan(const SubArgs& a, void* stream) {
     hipLaunchKernelGGL(k_sub_plan, dim3((unsigned)a.chunks), dim3(FG::THREADS), 0, static_cast<hipStream_t>(stream), a);
 }
