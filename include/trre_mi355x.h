@@ -56,7 +56,8 @@ extern "C" {
 #define TRRE_MODE_SPANS 8 /* where every match of every string starts and ends (finditer().span(), str.find, str.count): the positions
                            * of the same attempts, nothing of what they print.  NFT engine only; runs through
                            * trre_span_device_strings, trre_split_device_strings, trre_filter_device_strings,
-                           * trre_field_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and
+                           * trre_field_device_strings, trre_splitn_device_strings, trre_fieldn_device_strings and nothing
+                           * else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and
                            * stay TRRE_E_ARG, as they were) */
 #define TRRE_MODE_SUB 16 /* the first n matches of every string replaced by what they print, the rest of the string kept
                           * (sed 's/x/y/', re.sub(p, r, s, count), str.replace(p, r, n)): the spans table and the texts table over the
@@ -440,6 +441,59 @@ int trre_filter_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, cons
 int trre_field_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k,
                               uint8_t* d_out, size_t cap, int64_t* d_out_off, uint8_t* d_valid, size_t* n_valid,
                               size_t* out_len, void* stream);
+
+/* Split strings at the first or last matches only: trre_split_device_strings with a LIMIT — line.split('=', 1),
+ * re.split(p, s, maxsplit=n), s.str.split(p, n=1), s.rsplit('.', 1), s.str.rsplit(p, n=1), str.partition / rpartition, the first
+ * three columns of a log line and "the rest".  String i has c matches (s_r, e_r), r = 0 .. c - 1, exactly those of
+ * trre_span_device_strings (the string cut at its first NUL, empty matches counted, what the program prints playing no part).
+ * Match r CUTS exactly when limit < 0, or TRRE_SPLIT_FROM_END is clear and r < limit, or it is set and c - r <= limit.  limit
+ * is compared, never added or negated: any int64 is legal, INT64_MIN and INT64_MAX included; limit == 0 cuts nothing.  With cc
+ * cutting matches (cc = c when limit < 0, otherwise min(c, limit)) the string has cc + 1 pieces: the bytes outside the CUTTING
+ * matches, in order.  A match that does not cut stays in its piece as ordinary text ('=' with limit 1 on "a=b=c": "a", "b=c";
+ * '\.' with limit 1 from the end on "x.tar.gz": "x.tar", "gz"); a NUL and everything behind it stays in the last piece; an empty
+ * cutting match yields an empty piece where the split call would; an empty match that does not cut changes nothing.
+ *   d_out        cap bytes: the bytes of d_in outside the cutting matches, in order; *out_len = n minus those matches' bytes
+ *   d_piece_off  room for piece_cap + 1 entries, as the split call's; entry *n_pieces = *out_len
+ *   d_list_off   nrec + 1 entries: d_list_off[i] is the number of cutting matches in strings 0 .. i - 1, plus i;
+ *                d_list_off[nrec] = *n_pieces
+ * Two identities: with limit < 0, or limit >= every string's c, the three arrays are byte for byte trre_split_device_strings',
+ * with either flag value; with limit == 0, d_out is d_in, d_piece_off[i] = d_off[i] - d_off[0] and d_list_off[i] = i.
+ * Null rules, the size query, nrec == 0, TRRE_E_CAPACITY (exactly when *out_len > cap or *n_pieces > piece_cap: both sizes and
+ * d_list_off valid, d_out and d_piece_off not written at all), TRRE_E_DIVERGES, a string that holds a '\n', the offsets' check,
+ * overlaps (no in-place form), the 2^55 / 2^58 limits and a split-form scan in flight: word for word the split call's.  Refused
+ * before the device is touched, in this order: a null argument; a bit of `flags` other than TRRE_SPLIT_FROM_END; a program
+ * compiled with TRRE_MODE_SUB; any other program not compiled with TRRE_MODE_SPANS (all TRRE_E_ARG); TRRE_KERNEL_BACKTRACK
+ * forced (TRRE_E_UNSUPPORTED); the sizes; the overlaps.
+ * How: the span call's passes up to its totals, and its list offsets L, and nothing else of it, into an array of the library's
+ * own.  Match number j of the column, behind l newlines, is match r = j - L[l] of c = L[l + 1] - L[l]: the lane that owns a
+ * marker resolves the rule once, and a tile that starts inside a match once for that match — never per byte.  One count pass
+ * over the 16 KiB framed tiles gives the kept bytes and the cutting matches that close in every tile; their two exclusive sums'
+ * totals are *out_len and *n_pieces - nrec, read back in one synchronisation and checked before anything of the caller's is
+ * written.  One compaction pass copies every kept byte from d_in; the lane that owns the 0x02 of a cutting match, behind cb
+ * others and l newlines, stores d_piece_off[cb + 1 + l]; the lane that owns newline i, behind ca cutting matches,
+ * d_piece_off[ca + i + 1] and d_list_off[i + 1] = ca + i + 1; the markers of a match that does not cut store nothing.  Every
+ * byte and word is stored once.
+ * Device memory, kept by the (prog, device) until trre_free: the span call's, 8 (nrec + 1) bytes of list offsets, and two
+ * counters and their sums per framed tile (32 bytes per 16 KiB of the framed text).  Synchronous with respect to `stream`;
+ * trre_last_scan_flags as for the strings call. */
+#define TRRE_SPLIT_FROM_END 1u   /* the LAST `limit` matches cut (rsplit), not the first */
+int trre_splitn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t limit,
+                               uint32_t flags, uint8_t* d_out, size_t cap, int64_t* d_piece_off, size_t piece_cap,
+                               int64_t* d_list_off, size_t* n_pieces, size_t* out_len, void* stream);
+
+/* Field k of that limited split: trre_field_device_strings with `limit` and `flags` as trre_splitn_device_strings defines them —
+ * key and value of "k=v=w" ('=', limit 1: fields 0 and 1 are "k" and "v=w"), stem and extension ('\.', limit 1 from the end, on
+ * "x.tar.gz": field 0 is "x.tar", field -1 "gz"), str.partition / rpartition.  With cc the string's cutting matches: kk = k for
+ * k >= 0 and cc + 1 + k for k < 0; the field is valid exactly when 0 <= kk <= cc.  With m0 the first cutting match (0 from the
+ * front, c - cc from the end) the field starts at the string's start when kk = 0, otherwise at e_{m0 + kk - 1}, and ends at the
+ * string's end when kk = cc, otherwise at s_{m0 + kk}.  With limit < 0 the call returns what trre_field_device_strings returns.
+ * The outputs, the null rules, the size query, TRRE_E_CAPACITY, TRRE_E_DIVERGES and every refusal are the field call's; a bit of
+ * `flags` other than TRRE_SPLIT_FROM_END is refused (TRRE_E_ARG) behind the null arguments and before the program's mode.
+ * How: the field call's passes; only which marker stores a bound, and which strings have the field, follow the limited index
+ * arithmetic.  Device memory: the field call's. */
+int trre_fieldn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k,
+                               int64_t limit, uint32_t flags, uint8_t* d_out, size_t cap, int64_t* d_out_off, uint8_t* d_valid,
+                               size_t* n_valid, size_t* out_len, void* stream);
 
 /* Replaced strings: the same column of strings under a program compiled with TRRE_MODE_SUB, with SOME of every string's matches
  * replaced by what they print — sed 's/x/y/' (the first match only), re.sub(p, r, s, count), s.str.replace(p, r, n=1), SQL's

@@ -36,6 +36,7 @@ E_SYNTAX, E_UNDEFINED, E_EPS_CYCLE, E_TOO_BIG, E_UNSUPPORTED = -1, -2, -3, -4, -
 E_DEVICE, E_ARG, E_DIVERGES, E_CAPACITY = -6, -7, -8, -9
 
 FILTER_INVERT = 1
+SPLIT_FROM_END = 1
 
 
 class TrreError(RuntimeError):
@@ -103,6 +104,10 @@ def lib():
         L.trre_split_device_strings.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_filter_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_field_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_splitn_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_uint32, vp, sz, vp, sz, vp, ctypes.POINTER(sz),
+                                                 ctypes.POINTER(sz), vp]
+        L.trre_fieldn_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32, vp, sz, vp, vp,
+                                                 ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_sub_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_int64, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_nth_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
@@ -497,18 +502,27 @@ class Program:
         st, en, lo = starts.cpu().numpy().tolist(), ends.cpu().numpy().tolist(), list_off.cpu().numpy().tolist()
         return [[(st[j] - int(off[i]), en[j] - int(off[i])) for j in range(lo[i], lo[i + 1])] for i in range(len(recs))]
 
-    def split_strings(self, values, offsets, stream=None):
+    def split_strings(self, values, offsets, stream=None, *, limit=-1, from_end=False):
         """Split strings (trre_split_device_strings; a program compiled with mode="spans"): values and offsets as for
         scan_strings, no string holding a b"\\n".  Every string is cut at every match, as re.split cuts it.  Returns (out,
         piece_offsets, list_offsets): string i's pieces are numbers list_offsets[i] .. list_offsets[i + 1] - 1 (one more than
         its matches), and piece k is out[piece_offsets[k]:piece_offsets[k + 1]].  Two calls: the size query, then the one that
-        fills buffers of exactly that size."""
+        fills buffers of exactly that size.
+        limit >= 0 (trre_splitn_device_strings) cuts at the first `limit` matches of every string only, with from_end=True at
+        the last `limit`; a match that does not cut stays in its piece: limit=1 is line.split(sep, 1) and str.partition,
+        limit=1 with from_end=True s.rsplit(sep, 1) and str.rpartition, limit=n re.split(p, s, maxsplit=n) for n >= 1; limit=0
+        cuts nothing, and a negative limit cuts at every match.  With the defaults the call is trre_split_device_strings."""
         import torch
         n, nrec, s = _column(values, offsets, stream)
         list_off = torch.empty(nrec + 1, dtype=torch.int64, device=values.device)
         m, k = ctypes.c_size_t(), ctypes.c_size_t()
+        limited = limit != -1 or from_end
 
         def call(o, cap, po, pcap):
+            if limited:
+                return lib().trre_splitn_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, limit,
+                                                        SPLIT_FROM_END if from_end else 0, o, cap, po, pcap, list_off.data_ptr(),
+                                                        ctypes.byref(k), ctypes.byref(m), s)
             return lib().trre_split_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, o, cap, po, pcap,
                                                    list_off.data_ptr(), ctypes.byref(k), ctypes.byref(m), s)
 
@@ -518,10 +532,11 @@ class Program:
             return (out[:m], piece_off, list_off), (out.data_ptr(), m, piece_off.data_ptr(), k)
         return _query_then_fill(call, (None, 0, None, 0), alloc, (k, m), values.device)
 
-    def split_list(self, records, device=0):
-        """list of bytes in -> per string the list of its pieces (bytes), as re.split gives them (through split_strings)"""
+    def split_list(self, records, device=0, *, limit=-1, from_end=False):
+        """list of bytes in -> per string the list of its pieces (bytes), as re.split gives them (through split_strings; limit and
+        from_end as there)"""
         recs, off, values, offsets = _pack(records, device)
-        return _read_back(*self.split_strings(values, offsets))
+        return _read_back(*self.split_strings(values, offsets, limit=limit, from_end=from_end))
 
     def filter_strings(self, values, offsets, invert=False, stream=None):
         """Filtered strings (trre_filter_device_strings; a program compiled with mode="spans"): values and offsets as for
@@ -552,20 +567,28 @@ class Program:
         out, out_off, rows = self.filter_strings(values, offsets, invert=invert)
         return _read_back(out, out_off), rows.cpu().numpy().tolist()
 
-    def field_strings(self, values, offsets, k, stream=None, packed=False):
+    def field_strings(self, values, offsets, k, stream=None, packed=False, *, limit=-1, from_end=False):
         """Field k of every string (trre_field_device_strings; a program compiled with mode="spans"): values and offsets as for
         scan_strings, no string holding a b"\\n".  Every string is split at every match, as split_strings does, and ONE piece of
         it taken: piece k, or, for k < 0, piece k counted from the end (-1: the last), as s.str.split(p).str.get(k) and SQL's
         split_part.  Returns (out, out_offsets, valid): string i's field is out[out_offsets[i]:out_offsets[i + 1]], empty when the
         string has no such piece, and valid[i] says whether it has.  valid is a torch.bool tensor of nrec entries; with
         packed=True it is the Arrow validity bitmap as the library wrote it (uint8, 8 * ceil(nrec / 64) bytes, bit i & 7 of byte
-        i >> 3).  Two calls: the size query, then the one that fills a buffer of exactly that size."""
+        i >> 3).  Two calls: the size query, then the one that fills a buffer of exactly that size.
+        limit and from_end (trre_fieldn_device_strings) are split_strings': the field is piece k of that limited split — limit=1
+        with k=1 the value of b"key=v=w", limit=1, from_end=True with k=0 the stem of b"x.tar.gz".  With the defaults the call is
+        trre_field_device_strings."""
         import torch
         n, nrec, s = _column(values, offsets, stream)
         words = torch.zeros(max((nrec + 63) // 64, 1), dtype=torch.int64, device=values.device)     # (8-byte aligned)
         m, v = ctypes.c_size_t(), ctypes.c_size_t()
+        limited = limit != -1 or from_end
 
         def call(o, cap, oo):
+            if limited:
+                return lib().trre_fieldn_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, k, limit,
+                                                        SPLIT_FROM_END if from_end else 0, o, cap, oo, words.data_ptr(), ctypes.byref(v),
+                                                        ctypes.byref(m), s)
             return lib().trre_field_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, k, o, cap, oo,
                                                    words.data_ptr(), ctypes.byref(v), ctypes.byref(m), s)
 
@@ -575,11 +598,11 @@ class Program:
             return (out[:m], out_off), (out.data_ptr(), m, out_off.data_ptr())
         return _query_then_fill(call, (None, 0, None), alloc, (v, m), values.device) + (_validity(words, nrec, packed),)
 
-    def field_list(self, records, k, device=0):
+    def field_list(self, records, k, device=0, *, limit=-1, from_end=False):
         """list of bytes in -> list out: field k of every string (bytes), None where the string has no such piece (through
-        field_strings)"""
+        field_strings; limit and from_end as there)"""
         recs, off, values, offsets = _pack(records, device)
-        out, out_off, valid = self.field_strings(values, offsets, k)
+        out, out_off, valid = self.field_strings(values, offsets, k, limit=limit, from_end=from_end)
         return [b if ok else None for b, ok in zip(_read_back(out, out_off), valid.cpu().numpy().tolist())]
 
     def sub_strings(self, values, offsets, count=-1, first=0, stream=None):

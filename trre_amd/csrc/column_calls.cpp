@@ -1,6 +1,7 @@
 // column_calls.cpp — the calls on a column of records or strings (records_block.hpp): their shared host passes, one
 // function per call that queues its passes around the scan, and their entry points of the C ABI (include/trre_mi355x.h).  They reach
 // the scan core (runtime.cpp) through the names that runtime_state.hpp declares.
+#include <functional>
 #include <initializer_list>
 
 #include "runtime_state.hpp"
@@ -830,12 +831,80 @@ int trre_split_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     return split_on(p, c.st, d_in, n, d_off, nrec, d_out, cap, d_piece_off, piece_cap, d_list_off, n_pieces, out_len, static_cast<hipStream_t>(stream));
 }
 
+// the pieces between the first or last `limit` matches: steps 1 - 5 are the span call's, 6 its list offsets into the library's own
+// array; d_splitn_cnt holds cnt [2][tiles] and base [2][tiles + 1] of the kept bytes and the cutting matches per framed tile
+static int splitn_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t limit, uint32_t flags,
+                     uint8_t* d_out, size_t cap, int64_t* d_piece_off, size_t piece_cap, int64_t* d_list_off, size_t* n_pieces, size_t* out_len,
+                     hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    SpanMarks mk;
+    int rc = span_marks(p, st, d_in, n, d_off, nrec, false, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        HIP_TRY(hipMemsetAsync(d_list_off, 0, 8, s));
+        if (d_piece_off) HIP_TRY(hipMemsetAsync(d_piece_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    // 6. the span call's list offsets: which match of its string a marker belongs to, and of how many
+    SpanArgs& pa = mk.pa;
+    const int64_t ftiles = pa.tiles;
+    HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
+    HIP_TRY(cx->d_splitn_cnt.reserve((size_t)ftiles, (size_t)(4 * ftiles + 2) * 8));
+    pa.start = pa.end = nullptr; pa.list_off = cx->d_filter_lists; pa.n_match = 0; pa.lists_only = 1u;
+    launch_span_emit(pa, s);
+    // 7. the kept bytes and the cutting matches per framed tile and before it; the two totals in one read-back
+    SplitnArgs a{};
+    a.L = cx->d_filter_lists; a.limit = limit; a.flags = flags;
+    a.s.src = pa.src; a.s.total = pa.total; a.s.in = d_in; a.s.n = (int64_t)n; a.s.list_off = d_list_off; a.s.nrec = (int64_t)nrec;
+    a.s.tiles = ftiles; a.s.base = pa.base; a.s.kcnt = cx->d_splitn_cnt; a.s.kbase = a.s.kcnt + 2 * ftiles;
+    launch_splitn_count(a, s);
+    uint64_t tot[2] = {0, 0};
+    rc = scan_counts(a.s.kcnt, a.s.kbase, 2, ftiles, s, tot);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (tot[0] > n || tot[1] > mk.found) return fail(TRRE_E_DEVICE, "error: the cutting matches do not add up (internal)");
+    const size_t pieces = (size_t)tot[1] + nrec, kept = (size_t)tot[0];
+    if (n_pieces) *n_pieces = pieces;
+    if (out_len) *out_len = kept;
+    // 8. the pieces, where each starts and the list offsets — the list offsets alone when either does not fit
+    const bool over = kept > cap || pieces > piece_cap;
+    a.s.lists_only = over ? 1u : 0u;
+    if (!over) { a.s.out = d_out; a.s.out_len = (int64_t)kept; a.s.piece_off = d_piece_off; a.s.n_piece = (int64_t)pieces; }
+    launch_splitn_emit(a, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return over ? fail(TRRE_E_CAPACITY, "error: output buffer too small") : TRRE_OK;
+}
+
+int trre_splitn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t limit, uint32_t flags,
+                               uint8_t* d_out, size_t cap, int64_t* d_piece_off, size_t piece_cap, int64_t* d_list_off, size_t* n_pieces,
+                               size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_pieces) *n_pieces = 0;
+    if (!p || !d_off || !d_list_off || (n && !d_in) || (cap && !d_out) || (piece_cap && !d_piece_off)) return fail(TRRE_E_ARG, "error: null argument");
+    if (flags & ~TRRE_SPLIT_FROM_END) return fail(TRRE_E_ARG, "error: unknown flag (TRRE_SPLIT_FROM_END is the only one)");
+    if (int rc = spans_program(p, "split strings")) return rc;
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55) || piece_cap >= ((size_t)1 << 58)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    const size_t ob = (nrec + 1) * 8, pb = d_piece_off ? (piece_cap + 1) * 8 : 0, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the pieces are not made in place)");
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_list_off, ob}, {d_piece_off, pb}}))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return splitn_on(p, c.st, d_in, n, d_off, nrec, limit, flags, d_out, cap, d_piece_off, piece_cap, d_list_off, n_pieces, out_len,
+                     static_cast<hipStream_t>(stream));
+}
+
 // What the filter call and the field call do with the span call's marks: the list offsets, and nothing else of the span call
-// (k_span_emit, lists only), into the library's own array; the geometry of the INPUT's tiles; the field call's bounds (field: its
-// arguments, *a their .f), which read the span call's tiles; then d_rec carved for the input's tiles — behind the status word:
-// part [tiles + 1], cnt [2][tiles], base [2][tiles + 1] — into *a
+// (k_span_emit, lists only), into the library's own array; the geometry of the INPUT's tiles; bounds(pa): the field calls' launch of
+// their bounds' kernels (*a is the .f of their arguments; the filter call: nothing), which read the span call's tiles; then d_rec
+// carved for the input's tiles — behind the status word: part [tiles + 1], cnt [2][tiles], base [2][tiles + 1] — into *a
 static int filter_tiles(ScanCtx* cx, trre::SpanArgs& pa, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, hipStream_t s,
-                        trre::FilterArgs* a, const trre::FieldArgs* field) {
+                        trre::FilterArgs* a, const std::function<void(const trre::SpanArgs&)>& bounds) {
     HIP_TRY(cx->d_filter_lists.reserve(nrec + 1, (nrec + 1) * 8));
     pa.start = pa.end = nullptr; pa.list_off = cx->d_filter_lists; pa.n_match = 0; pa.lists_only = 1u;
     trre::launch_span_emit(pa, s);
@@ -844,7 +913,7 @@ static int filter_tiles(ScanCtx* cx, trre::SpanArgs& pa, const uint8_t* d_in, si
     const int64_t tiles = std::max<int64_t>((a0 + (int64_t)n + T - 1) / T, 1);
     a->in_v0 = d_in - a0; a->vbeg = a0; a->n = (int64_t)n; a->off = d_off; a->loff = cx->d_filter_lists; a->nrec = (int64_t)nrec;
     a->tiles = tiles;
-    if (field) trre::launch_field_bounds(pa, *field, s);
+    bounds(pa);
     RecCarve c;                                             // (room as for 2 tiles + 1: 6 tiles + 6 words)
     const int rc = rec_carve(cx, 2 * tiles + 1, &c);
     if (rc) return rc;
@@ -869,7 +938,7 @@ static int filter_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t 
     //    and bytes per tile and before it; the two totals in one read-back
     FilterArgs a{};
     a.invert = (flags & TRRE_FILTER_INVERT) ? 1u : 0u;
-    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a, nullptr);
+    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a, [](const SpanArgs&) {});
     if (rc) return rc;
     launch_filter_count(a, s);
     uint64_t tot[2] = {0, 0};
@@ -930,7 +999,7 @@ static int field_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n
     HIP_TRY(cx->d_field_bounds.reserve(nrec, 2 * nrec * 8));
     FieldArgs a{};
     a.k = k; a.lo = cx->d_field_bounds; a.hi = a.lo + nrec; a.valid = d_valid; a.words = (int64_t)((nrec + 63) / 64);
-    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a.f, &a);
+    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a.f, [&](const SpanArgs& pa) { launch_field_bounds(pa, a, s); });
     if (rc) return rc;
     // 8. over tiles of the INPUT: the first string of every tile, the strings with the field and the field bytes per tile and before
     //    it; the two totals in one read-back
@@ -975,6 +1044,70 @@ int trre_field_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const
     if (const int rc = c.begin(p)) return rc;
     return field_on(p, c.st, d_in, n, d_off, nrec, k, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_valid, out_len,
                     static_cast<hipStream_t>(stream));
+}
+
+// field k of the split at the first or last `limit` matches: the field call's steps, with the limited index arithmetic in the
+// bounds (7) and the verdicts (8)
+static int fieldn_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k, int64_t limit,
+                     uint32_t flags, uint8_t* d_out, size_t cap, int64_t* d_out_off, uint64_t* d_valid, size_t* n_valid, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    SpanMarks mk;
+    int rc = span_marks(p, st, d_in, n, d_off, nrec, false, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    HIP_TRY(cx->d_field_bounds.reserve(nrec, 2 * nrec * 8));
+    FieldnArgs fn{};
+    fn.limit = limit; fn.flags = flags;
+    FieldArgs& a = fn.a;
+    a.k = k; a.lo = cx->d_field_bounds; a.hi = a.lo + nrec; a.valid = d_valid; a.words = (int64_t)((nrec + 63) / 64);
+    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a.f, [&](const SpanArgs& pa) { launch_fieldn_bounds(pa, fn, s); });
+    if (rc) return rc;
+    launch_fieldn_count(fn, s);
+    uint64_t tot[2] = {0, 0};
+    rc = scan_counts(a.f.cnt, a.f.base, 2, a.f.tiles, s, tot);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (tot[0] > nrec || tot[1] > n) return fail(TRRE_E_DEVICE, "error: the fields do not add up (internal)");
+    const size_t bytes = (size_t)tot[1];
+    if (n_valid) *n_valid = (size_t)tot[0];
+    if (out_len) *out_len = bytes;
+    if (bytes > cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    if (d_out_off) {
+        a.f.out = d_out; a.f.out_len = (int64_t)bytes; a.f.out_off = d_out_off;
+        launch_field_emit(a, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return TRRE_OK;
+}
+
+int trre_fieldn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k, int64_t limit, uint32_t flags,
+                               uint8_t* d_out, size_t cap, int64_t* d_out_off, uint8_t* d_valid, size_t* n_valid, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (n_valid) *n_valid = 0;
+    if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (!d_out_off && (d_out || cap)) || (nrec && !d_valid))
+        return fail(TRRE_E_ARG, "error: null argument");
+    if (flags & ~TRRE_SPLIT_FROM_END) return fail(TRRE_E_ARG, "error: unknown flag (TRRE_SPLIT_FROM_END is the only one)");
+    if (int rc = spans_program(p, "field strings")) return rc;
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    if (reinterpret_cast<uintptr_t>(d_valid) & 7u) return fail(TRRE_E_ARG, "error: the validity bitmap must be 8-byte aligned (it is written as 64-bit words)");
+    const size_t ob = (nrec + 1) * 8, pb = d_out_off ? ob : 0, vb = (nrec + 63) / 64 * 8, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the fields are not made in place)");
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_out_off, pb}}))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    if (any_overlap({{d_in, n}, {d_out, cb}, {d_off, ob}, {d_out_off, pb}}, {{d_valid, vb}}))
+        return fail(TRRE_E_ARG, "error: the validity bitmap overlaps the data or an offsets array");
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return fieldn_on(p, c.st, d_in, n, d_off, nrec, k, limit, flags, d_out, cap, d_out_off, reinterpret_cast<uint64_t*>(d_valid), n_valid, out_len,
+                     static_cast<hipStream_t>(stream));
 }
 
 // ---- replaced strings (records_block.hpp) -----------------------------------------------------------------------------------

@@ -18,6 +18,8 @@ struct SpanArgs;
 struct SplitArgs;
 struct FilterArgs;
 struct FieldArgs;
+struct SplitnArgs;
+struct FieldnArgs;
 struct SubArgs;
 struct NthArgs;
 
@@ -133,6 +135,15 @@ void launch_filter_emit(const FilterArgs& a, void* stream);
 void launch_field_bounds(const SpanArgs& sp, const FieldArgs& a, void* stream);
 void launch_field_count(const FieldArgs& a, void* stream);
 void launch_field_emit(const FieldArgs& a, void* stream);
+// split at the first or last matches only (records_block.hpp), behind launch_span_count with its scans and launch_span_emit's list
+// offsets (a.L): the kept bytes and the cutting matches per framed tile (a.s.kcnt [2][tiles]), then — behind their two exclusive
+// scans (a.s.kbase) — the pieces' bytes, the piece offsets and the list offsets
+void launch_splitn_count(const SplitnArgs& a, void* stream);
+void launch_splitn_emit(const SplitnArgs& a, void* stream);
+// field k of that split: launch_field_bounds and launch_field_count with the limited index arithmetic; the emit pass is
+// launch_field_emit(a.a)
+void launch_fieldn_bounds(const SpanArgs& sp, const FieldnArgs& a, void* stream);
+void launch_fieldn_count(const FieldnArgs& a, void* stream);
 // replaced strings (records_block.hpp), behind launch_span_emit's spans and list offsets and launch_find_unframe's texts: the
 // selection bits and the selected matches, texts' bytes and matched bytes per chunk of sub_chunk_matches() matches (a.cnt; a.status
 // |= 1 when the arrays are out of order); then — behind their three exclusive scans — where every segment starts; the output

@@ -1179,6 +1179,207 @@ TRRE_HD void field_emit_offsets(const FieldArgs& a, const FilterTile<G>& t, int6
             a.f.out_off[i + 1] = k0 + (int64_t)filter_kept_below<G>(bits16, pv, a.f.off[i + 1] + a.f.vbeg - t.s0);
 }
 
+// ---- split at the first or last matches only (trre_splitn_device_strings, trre_fieldn_device_strings) ----------------------
+// The split call with a RULE: match r of a string's c matches CUTS exactly when splitn_cuts says so; a match that does not cut
+// stays in its piece as ordinary text.  So the depth of the split call counts the cutting matches alone, a position byte is kept
+// exactly when it lies outside every CUTTING match, and the markers of a match that does not cut are dropped and store nothing.
+// The rule needs the match's rank in its string and, from the end, the string's matches: A number j (B number j) with l '\n'
+// before it is match r = j - L[l] of c = L[l + 1] - L[l], L the span call's list offsets in an array of the library's own
+// (k_span_emit, lists only).  It is resolved once per marker — never per byte — and once per tile that starts inside a match
+// (base[0][b] > base[1][b]: match base[0][b] - 1 of string base[2][b], a tile may lie wholly inside it and hold no marker).
+// With kp the kept bytes and cb the cutting B before framed position q:
+//     kept byte at q        out[kp] = in[q - a - b - l]
+//     cutting B at q        piece_off[cb + 1 + l] = kp
+//     '\n' number i at q    piece_off[cb + i + 1] = kp,  list_off[i + 1] = cb + i + 1      (depth 0: every cutting A before is closed)
+// The passes, behind k_span_count and its three scans and k_span_emit's L:
+//   k_splitn_count  k_span_emit's three mark images, scans and prefixes; every marker lane resolves the rule and sets its bit of the
+//                   CUT image (LDS, zeroed before); a workgroup scan of the cut bits per thread segment gives every segment its
+//                   depth on entry; kcnt[2][tiles]: the tile's kept bytes and cutting B;  k_chunk_scan twice: kbase[2][tiles + 1];
+//                   the totals are out_len and n_pieces - nrec, read back and checked before anything of the caller's is stored
+//   k_splitn_emit   the same images, the kept image and the scan of kept bytes and cutting B (one word: a tile holds fewer than
+//                   65 536 bytes); then a wave takes 64 framed bytes at a time, as k_split_emit does
+// Who writes which byte and word: entry 0 of both arrays thread 0 of tile 0; every output byte the lane that owns its kept position
+// byte; every other word the lane that owns its cutting B or '\n', once.  An A lane and the B of a match that does not cut store
+// nothing.  lists_only: out and piece_off are not stored at all.
+constexpr uint32_t kSplitFromEnd = 1u;                // TRRE_SPLIT_FROM_END
+
+// THE RULE: does match r of a string's c matches cut.  (limit is compared, never added or negated: any int64 is legal)
+TRRE_HD bool splitn_cuts(int64_t r, int64_t c, int64_t limit, uint32_t flags) {
+    if (limit < 0) return true;
+    return (flags & kSplitFromEnd) ? c - r <= limit : r < limit;
+}
+// ... and how many of the c do: they are the first or the last so many
+TRRE_HD int64_t splitn_cutting(int64_t c, int64_t limit) { return limit < 0 || limit > c ? c : limit; }
+
+struct SplitnArgs {
+    SplitArgs s;            // as the split call has them; kcnt: [2][tiles] kept bytes, cutting B per tile; kbase: [2][tiles + 1]
+    const int64_t* L;       // [nrec + 1] the span call's list offsets
+    int64_t limit;
+    uint32_t flags;
+};
+
+// does match j of the column, which lies in string l, cut (from the front the string's matches are not looked up)
+TRRE_HD bool splitn_match_cuts(const SplitnArgs& a, int64_t j, int64_t l) {
+    if (a.limit < 0) return true;
+    if (l < 0 || l >= a.s.nrec) return false;         // (never: the newline total was checked against nrec before)
+    const int64_t l0 = a.L[l];
+    const int64_t c = (a.flags & kSplitFromEnd) ? a.L[l + 1] - l0 : 0;
+    return splitn_cuts(j - l0, c, a.limit, a.flags);
+}
+// 1 when tile b starts inside a cutting match (the same for every thread of the workgroup)
+TRRE_HD uint32_t splitn_tile_depth(const SplitnArgs& a, int64_t b) {
+    const int64_t na = (int64_t)a.s.base[b], nb = (int64_t)a.s.base[a.s.tiles + 1 + b];
+    if (na <= nb) return 0u;
+    return splitn_match_cuts(a, na - 1, (int64_t)a.s.base[2 * (a.s.tiles + 1) + b]) ? 1u : 0u;
+}
+// behind the barrier that completes bits and pv: the bits of the tile's cutting markers (cut32: TILE / 32 words, zeroed before)
+template <class G>
+TRRE_HD void splitn_cut_markers(const SplitnArgs& a, int64_t b, int tid, const uint16_t* bits, const uint32_t* pv_ab, const uint32_t* pv_nl,
+                                uint32_t* cut32) {
+    SpanArgs sp{};
+    sp.base = a.s.base; sp.tiles = a.s.tiles;
+    span_each_marker<G>(sp, b, tid, bits, pv_ab, pv_nl, [&](int kind, int64_t na, int64_t nb, int64_t nl, int64_t pos) {
+        if (kind == 2 || !splitn_match_cuts(a, kind == 0 ? na : nb, nl)) return;
+        const int64_t x = pos + na + nb + nl - b * G::TILE;           // the marker's byte in the tile
+        TRRE_REC_LDS_OR(cut32 + (x >> 5), 1u << (uint32_t)(x & 31));
+    });
+}
+// cutting markers | cutting B << 16 in the thread's rank segment, vectors [tid * VECS, tid * VECS + VECS)
+template <class G>
+TRRE_HD uint32_t splitn_seg_cut(const uint16_t* bits, const uint16_t* cut, int tid) {
+    static_assert(G::TILE < 65536, "two counts of a tile share a 32-bit word");
+    uint32_t c = 0;
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        c += rec_popc(cut[q]) | rec_popc((uint32_t)cut[q] & bits[G::NVEC + q]) << 16;
+    }
+    return c;
+}
+// the kept bits of the thread's rank segment (d0: splitn_tile_depth; pre_c: splitn_seg_cut before the segment in the tile); kept:
+// [NVEC] 16-bit masks, or null (k_splitn_count).  Returns the segment's kept bytes
+template <class G>
+TRRE_HD uint32_t splitn_seg_kept(const SplitnArgs& a, int64_t b, int tid, const uint16_t* bits, const uint16_t* cut, uint32_t d0, uint32_t pre_c,
+                                 uint16_t* kept) {
+    uint32_t d = (d0 + (pre_c & 0xffffu)) & 1u;
+    uint32_t c = 0;
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        const int64_t v = b * G::TILE + 16 * (int64_t)q;
+        const uint32_t mk = (uint32_t)bits[q] | bits[G::NVEC + q], cm = cut[q], nl = bits[2 * G::NVEC + q];
+        const uint32_t ok = v < a.s.total ? rec_valid16(v, 0, a.s.total) : 0u;
+        const uint32_t kp = ~(split_odd_below16(cm) ^ (0u - d)) & ~mk & ~nl & ok;
+        if (kept) kept[q] = (uint16_t)kp;
+        c += rec_popc(kp);
+        d ^= rec_popc(cm) & 1u;
+    }
+    return c;
+}
+// kept bytes | cutting B << 16 before each of the thread's segment vectors (pre_k, pre_c: before the segment)
+template <class G>
+TRRE_HD void splitn_fill_pv(const uint16_t* bits, const uint16_t* cut, const uint16_t* kept, uint32_t pre_k, uint32_t pre_c, int tid, uint32_t* pv_kc) {
+    uint32_t run = pre_k | (pre_c >> 16) << 16;
+    for (int k = 0; k < G::VECS; ++k) {
+        const int q = tid * G::VECS + k;
+        pv_kc[q] = run;
+        run += rec_popc(kept[q]) | rec_popc((uint32_t)cut[q] & bits[G::NVEC + q]) << 16;
+    }
+}
+// k_splitn_emit, behind the barrier that completes the five images and the three pv: the tile's bytes and words
+template <class G>
+TRRE_HD void splitn_emit_pieces(const SplitnArgs& a, int64_t b, int tid, const uint16_t* bits, const uint16_t* cut, const uint16_t* kept,
+                                const uint32_t* pv_ab, const uint32_t* pv_nl, const uint32_t* pv_kc) {
+    static_assert(G::THREADS % 64 == 0 && G::NVEC % 4 == 0, "a wave takes 64-byte pieces of the tile");
+    constexpr int kPieces = G::NVEC / 4, kWaves = G::THREADS / 64;
+    const SplitArgs& s = a.s;
+    const int lane = tid & 63;
+    const int64_t s0 = b * G::TILE;
+    const int64_t a0 = (int64_t)s.base[b], b0 = (int64_t)s.base[s.tiles + 1 + b], l0 = (int64_t)s.base[2 * (s.tiles + 1) + b];
+    const int64_t k0 = (int64_t)s.kbase[b], c0 = (int64_t)s.kbase[s.tiles + 1 + b];
+    if (b == 0 && tid == 0) {
+        s.list_off[0] = 0;
+        if (!s.lists_only) s.piece_off[0] = 0;
+    }
+    for (int k = tid >> 6; k < kPieces; k += kWaves) {
+        const uint64_t wa = span_word(bits, k), wb = span_word(bits + G::NVEC, k), wl = span_word(bits + 2 * G::NVEC, k);
+        const uint64_t wk = span_word(kept, k), wc = span_word(cut, k) & wb;
+        if (!(((s.lists_only ? wl : wc | wl | wk) >> lane) & 1u)) continue;
+        const uint64_t below = (1ull << lane) - 1ull;
+        const int64_t nl = l0 + (int64_t)pv_nl[4 * k] + (int64_t)match_popc64(wl & below);
+        const int64_t kp = k0 + (int64_t)(pv_kc[4 * k] & 0xffffu) + (int64_t)match_popc64(wk & below);
+        const int64_t cb = c0 + (int64_t)(pv_kc[4 * k] >> 16) + (int64_t)match_popc64(wc & below);
+        // (never beyond: the totals were checked against n, the pieces and nrec before this pass)
+        if ((wk >> lane) & 1u) {
+            const int64_t na = a0 + (int64_t)(pv_ab[4 * k] & 0xffffu) + (int64_t)match_popc64(wa & below);
+            const int64_t nb = b0 + (int64_t)(pv_ab[4 * k] >> 16) + (int64_t)match_popc64(wb & below);
+            const int64_t at = s0 + 64 * (int64_t)k + lane - na - nb - nl;
+            if (kp < s.out_len && at >= 0 && at < s.n) s.out[kp] = s.in[at];
+        } else if ((wc >> lane) & 1u) {
+            if (cb + 1 + nl <= s.n_piece) s.piece_off[cb + 1 + nl] = kp;
+        } else if (nl < s.nrec) {
+            s.list_off[nl + 1] = cb + nl + 1;
+            if (!s.lists_only && cb + nl + 1 <= s.n_piece) s.piece_off[cb + nl + 1] = kp;
+        }
+    }
+}
+
+// Field k of that split: the field call with the string's cc = splitn_cutting(c) cutting matches in place of its c.  They are the
+// matches m0 .. m0 + cc - 1 of the string, m0 = 0 from the front and c - cc from the end; piece kk = k (k >= 0) or cc + 1 + k
+// (k < 0) is there exactly when kk lies in [0, cc]; it starts at the string's start when kk = 0, otherwise where match
+// m0 + kk - 1 ends, and ends at the string's end when kk = cc, otherwise where match m0 + kk starts.  Only which marker stores a
+// bound is new (k_fieldn_init, k_fieldn_pick, and the verdicts of k_fieldn_count); the emit pass is the field call's.
+struct FieldnArgs {
+    FieldArgs a;            // as the field call has them
+    int64_t limit;
+    uint32_t flags;
+};
+
+// the piece k selects in string i; true when the string has it.  (cc + 1 > 0 > k: the sum cannot overflow; 0 <= m0 <= c)
+TRRE_HD bool fieldn_index(const FieldnArgs& a, int64_t i, int64_t& kk, int64_t& cc, int64_t& m0) {
+    const int64_t c = a.a.f.loff[i + 1] - a.a.f.loff[i];
+    cc = splitn_cutting(c, a.limit);
+    m0 = (a.flags & kSplitFromEnd) ? c - cc : 0;
+    kk = a.a.k >= 0 ? a.a.k : cc + 1 + a.a.k;
+    return kk >= 0 && kk <= cc;
+}
+// k_fieldn_init, one lane: the verdict, and the bounds that no marker stores
+TRRE_HD bool fieldn_init(const FieldnArgs& a, int64_t i) {
+    int64_t kk, cc, m0;
+    const bool has = fieldn_index(a, i, kk, cc, m0);
+    const int64_t s = a.a.f.off[i], e = a.a.f.off[i + 1];
+    if (!has) {
+        a.a.lo[i] = a.a.hi[i] = e;
+    } else {
+        if (kk == 0) a.a.lo[i] = s;
+        if (kk == cc) a.a.hi[i] = e;
+    }
+    return has;
+}
+// k_fieldn_pick: the bounds the tile's markers own.  The A of the string's match m0 + kk ends piece kk (kk < cc); the B of its
+// match m0 + kk - 1 starts it (kk > 0)
+template <class G>
+TRRE_HD void fieldn_pick_markers(const FieldnArgs& a, const SpanArgs& sp, int64_t b, int tid, const uint16_t* bits, const uint32_t* pv_ab,
+                                 const uint32_t* pv_nl) {
+    span_each_marker<G>(sp, b, tid, bits, pv_ab, pv_nl, [&](int kind, int64_t na, int64_t nb, int64_t nl, int64_t pos) {
+        if (kind == 2 || nl >= a.a.f.nrec) return;        // (never beyond: the newline total was checked against nrec before)
+        int64_t kk, cc, m0;
+        if (!fieldn_index(a, nl, kk, cc, m0)) return;
+        const int64_t r = (kind == 0 ? na : nb) - a.a.f.loff[nl];
+        if (kind == 0 ? (kk < cc && r == m0 + kk) : (kk > 0 && r == m0 + kk - 1)) (kind == 0 ? a.a.hi : a.a.lo)[nl] = pos;
+    });
+}
+// k_fieldn_count: field_count_strings with the limited verdict
+template <class G>
+TRRE_HD void fieldn_count_strings(const FieldnArgs& a, const FilterTile<G>& t, int tid, uint64_t& valid, uint64_t& bytes) {
+    valid = bytes = 0;
+    const int64_t hi = t.hi(tid);
+    for (int64_t i = t.lo(tid); i < hi; ++i) {
+        int64_t kk, cc, m0;
+        if (fieldn_index(a, i, kk, cc, m0)) ++valid;
+        bytes += field_clip(a.a, i, t.t0, t.t1);
+    }
+    if (tid == 0 && t.i1 < a.a.f.nrec) bytes += field_clip(a.a, t.i1, t.t0, t.t1);
+}
+
 // ---- replaced strings (trre_sub_device_strings) ----------------------------------------------------------------------------
 // Some of every string's matches replaced by what they print: a splice of two sources the library already has.  The span call's
 // emit pass leaves, in arrays of the library's own, S[j], E[j] (where match j of the column starts and ends in d_in) and the list

@@ -1857,6 +1857,63 @@ __global__ __launch_bounds__(SG::THREADS) void k_split_emit(SplitArgs a) {
     split_emit_pieces<SG>(a, b, tid, bits, kept, pv_ab, pv_nl, pv_k);
 }
 
+// ---- split at the first or last matches only (records_block.hpp; column_calls.cpp: trre_splitn_device_strings) -------------
+// The tile's marks, scans and prefixes as span_tile_marks makes them, the cut image and the scan of its bits per thread segment,
+// then f(b, tid, bits, cut, pv_ab, pv_nl, pre_c, wtot — free again for a scan of f's own): what k_splitn_count and k_splitn_emit share.  Barriers: behind split_mark_vecs
+// and the zeroing of the cut image; the scans' own; behind pv, which the marker lanes read across threads; behind the marker
+// lanes' ORs into the cut image, which every segment's thread reads next; the last scan's own.
+template <class F>
+__device__ __forceinline__ void splitn_tile_cuts(const SplitnArgs& a, F f) {
+    __shared__ uint16_t bits[3 * SG::NVEC];
+    __shared__ uint32_t cut32[SG::NVEC / 2];
+    __shared__ uint32_t pv_ab[SG::NVEC];
+    __shared__ uint32_t pv_nl[SG::NVEC];
+    __shared__ uint32_t pre_ab[SG::THREADS];
+    __shared__ uint32_t pre_nl[SG::THREADS];
+    __shared__ uint32_t pre_c[SG::THREADS];
+    __shared__ uint32_t wtot[SG::THREADS / kWave];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    split_mark_vecs<SG>(a.s, b, tid, bits);
+    for (int k = tid; k < SG::NVEC / 2; k += SG::THREADS) cut32[k] = 0;
+    __syncthreads();
+    uint32_t ab, nl;
+    span_seg_count<SG>(bits, tid, ab, nl);
+    rec_block_scan(ab, pre_ab, wtot);
+    rec_block_scan(nl, pre_nl, wtot);
+    span_fill_pv<SG>(bits, pre_ab[tid], pre_nl[tid], tid, pv_ab, pv_nl);
+    __syncthreads();
+    splitn_cut_markers<SG>(a, b, tid, bits, pv_ab, pv_nl, cut32);
+    __syncthreads();
+    const uint16_t* cut = reinterpret_cast<const uint16_t*>(cut32);
+    rec_block_scan(splitn_seg_cut<SG>(bits, cut, tid), pre_c, wtot);
+    f(b, tid, bits, cut, pv_ab, pv_nl, pre_c[tid], wtot);
+}
+
+// The kept bytes and the cutting B per framed tile.
+__global__ __launch_bounds__(SG::THREADS) void k_splitn_count(SplitnArgs a) {
+    splitn_tile_cuts(a, [&](int64_t b, int tid, const uint16_t* bits, const uint16_t* cut, const uint32_t*, const uint32_t*, uint32_t pre_c, uint32_t*) {
+        const uint64_t c[2] = {splitn_seg_kept<SG>(a, b, tid, bits, cut, splitn_tile_depth(a, b), pre_c, nullptr),
+                               splitn_seg_cut<SG>(bits, cut, tid) >> 16};
+        tile_totals<uint32_t>(c, a.s.kcnt, a.s.tiles, b);
+    });
+}
+
+// The pieces' bytes, where each piece starts and the list offsets.  The kept image is written and read by its segment's thread
+// until the last barrier, which completes it and pv_kc for splitn_emit_pieces.
+__global__ __launch_bounds__(SG::THREADS) void k_splitn_emit(SplitnArgs a) {
+    __shared__ uint16_t kept[SG::NVEC];
+    __shared__ uint32_t pv_kc[SG::NVEC];
+    __shared__ uint32_t pre_k[SG::THREADS];
+    splitn_tile_cuts(a, [&](int64_t b, int tid, const uint16_t* bits, const uint16_t* cut, const uint32_t* pv_ab, const uint32_t* pv_nl, uint32_t pre_c,
+                            uint32_t* wtot) {
+        rec_block_scan(splitn_seg_kept<SG>(a, b, tid, bits, cut, splitn_tile_depth(a, b), pre_c, kept), pre_k, wtot);
+        splitn_fill_pv<SG>(bits, cut, kept, pre_k[tid], pre_c, tid, pv_kc);
+        __syncthreads();
+        splitn_emit_pieces<SG>(a, b, tid, bits, cut, kept, pv_ab, pv_nl, pv_kc);
+    });
+}
+
 // ---- filtered strings (records_block.hpp; runtime.cpp: trre_filter_device_strings) -----------------------------------------
 using FG = StrGeoDev;
 static_assert(FG::THREADS == RG::THREADS && FG::THREADS % kWave == 0, "rec_block_scan");
@@ -1963,6 +2020,31 @@ __global__ __launch_bounds__(FG::THREADS) void k_field_emit(FieldArgs a) {
                      [&](const FilterTile<FG>& t, int64_t b, int tid, const uint16_t* bits16, const uint32_t* pv) {
                          field_emit_offsets<FG>(a, t, b, tid, bits16, pv);
                      });
+}
+
+// ---- field k of a limited split (records_block.hpp; column_calls.cpp: trre_fieldn_device_strings) ------------------------
+// k_field_init, k_field_pick and k_field_count with the limited index arithmetic; the emit pass is k_field_emit itself.
+__global__ __launch_bounds__(kMatchThreads) void k_fieldn_init(FieldnArgs a, int64_t groups) {
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const int64_t i = g * kMatchThreads + tid;
+        const bool has = i < a.a.f.nrec && fieldn_init(a, i);
+        const uint64_t word = __ballot(has);
+        const int64_t at = g * (kMatchThreads / kWave) + w;
+        if (lane == 0 && at < a.a.words) a.a.valid[at] = word;
+    }
+}
+
+__global__ __launch_bounds__(SG::THREADS) void k_fieldn_pick(SpanArgs sp, FieldnArgs a) {
+    span_tile_marks(sp, [&](int64_t b, int tid, const uint16_t* bits, const uint32_t* pv_ab, const uint32_t* pv_nl) {
+        fieldn_pick_markers<SG>(a, sp, b, tid, bits, pv_ab, pv_nl);
+    });
+}
+
+__global__ __launch_bounds__(FG::THREADS) void k_fieldn_count(FieldnArgs a) {
+    uint64_t c[2];                                   // valid, bytes
+    fieldn_count_strings<FG>(a, FilterTile<FG>(a.a.f, blockIdx.x), threadIdx.x, c[0], c[1]);
+    tile_totals<uint64_t>(c, a.a.f.cnt, a.a.f.tiles, blockIdx.x);
 }
 
 // ---- replaced strings (records_block.hpp; runtime.cpp: trre_sub_device_strings) --------------------------------------------
@@ -2124,6 +2206,24 @@ void launch_split_count(const SplitArgs& a, void* stream) {
 }
 void launch_split_emit(const SplitArgs& a, void* stream) {
     hipLaunchKernelGGL(k_split_emit, dim3((unsigned)a.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+
+void launch_splitn_count(const SplitnArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_splitn_count, dim3((unsigned)a.s.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_splitn_emit(const SplitnArgs& a, void* stream) {
+    hipLaunchKernelGGL(k_splitn_emit, dim3((unsigned)a.s.tiles), dim3(SG::THREADS), 0, static_cast<hipStream_t>(stream), a);
+}
+void launch_fieldn_bounds(const SpanArgs& sp, const FieldnArgs& a, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t groups = (a.a.f.nrec + kMatchThreads - 1) / kMatchThreads;
+    hipLaunchKernelGGL(k_fieldn_init, dim3((unsigned)(groups < 1 ? 1 : groups > 256 * 16 ? 256 * 16 : groups)), dim3(kMatchThreads), 0, s, a, groups);
+    hipLaunchKernelGGL(k_fieldn_pick, dim3((unsigned)sp.tiles), dim3(SG::THREADS), 0, s, sp, a);
+}
+void launch_fieldn_count(const FieldnArgs& a, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_filter_part, dim3((unsigned)((a.a.f.tiles + 1 + 255) / 256)), dim3(256), 0, s, a.a.f);
+    hipLaunchKernelGGL(k_fieldn_count, dim3((unsigned)a.a.f.tiles), dim3(FG::THREADS), 0, s, a);
 }
 
 void launch_span_count(const SpanArgs& a, void* stream) {
