@@ -56,8 +56,8 @@ extern "C" {
 #define TRRE_MODE_SPANS 8 /* where every match of every string starts and ends (finditer().span(), str.find, str.count): the positions
                            * of the same attempts, nothing of what they print.  NFT engine only; runs through
                            * trre_span_device_strings, trre_split_device_strings, trre_filter_device_strings,
-                           * trre_field_device_strings, trre_splitn_device_strings, trre_fieldn_device_strings and nothing
-                           * else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and
+                           * trre_field_device_strings, trre_splitn_device_strings, trre_fieldn_device_strings,
+                           * trre_trim_device_strings and nothing else.  (8, not 5: 5, 6 and 7 read as sums of the modes above and
                            * stay TRRE_E_ARG, as they were) */
 #define TRRE_MODE_SUB 16 /* the first n matches of every string replaced by what they print, the rest of the string kept
                           * (sed 's/x/y/', re.sub(p, r, s, count), str.replace(p, r, n)): the spans table and the texts table over the
@@ -494,6 +494,57 @@ int trre_splitn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, cons
 int trre_fieldn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, int64_t k,
                                int64_t limit, uint32_t flags, uint8_t* d_out, size_t cap, int64_t* d_out_off, uint8_t* d_valid,
                                size_t* n_valid, size_t* out_len, void* stream);
+
+/* Trimmed strings: the same column of strings under a program compiled with TRRE_MODE_SPANS, every string without the match that
+ * touches its start and the match that touches its end — s.str.strip() / lstrip / rstrip, SQL's TRIM(LEADING | TRAILING | BOTH ..
+ * FROM s), removeprefix / removesuffix, regexp_replace(s, '^P|P$', '') — as a flat column with one entry per string.  trre's
+ * grammar has no anchors; this call is the anchored form of the span call's matches.  The definition rests on the spans of
+ * trre_span_device_strings: string i has bytes s of length len, the UNCUT length (a NUL and what follows are part of it), and the
+ * spans (s_0, e_0) .. (s_{c-1}, e_{c-1}), relative to the string, from the attempts on s cut at its first NUL.  Then
+ *     lo = max{ e_j : s_j == 0 }     with TRRE_TRIM_LEFT in `flags`; otherwise, and when no match starts at 0, lo = 0
+ *     hi = min{ s_j : e_j == len }   with TRRE_TRIM_RIGHT in `flags`; otherwise, and when no match ends at len, hi = len
+ * and the entry is s[lo : max(lo, hi)].  The min matters for a pattern that matches the empty string: 'x*' on "xxbxx" has the
+ * spans (0,2) (2,2) (3,5) (5,5); (3,5) and (5,5) both end at 5, and the entry is "b", as re.sub('^x*|x*$', '', s) gives.  At most
+ * one match starts at 0, and at most two end at len: a non-empty one and the empty tail attempt behind it; so the right side
+ * depends on the string's last two matches only.  A string that holds a NUL is never trimmed on the right (every span ends at or
+ * before the NUL); it is still trimmed on the left, and what is kept keeps the NUL and everything behind it (' +' on " a\0 ":
+ * "a\0 ").  A string that is one match (' +' on three spaces, '(cat|dog)' on "dogcat") becomes empty: lo = len, hi = 0, the entry
+ * s[len:len].  Only ONE match is removed from each side: a form that trims repeated matches is the caller's to write, as (P)+.
+ * What the program prints plays no part.
+ *   flags      TRRE_TRIM_LEFT, TRRE_TRIM_RIGHT or both; 0 and any other bit are refused (TRRE_E_ARG)
+ *   d_out      cap bytes: the entries, concatenated in input order; *out_len (may be null) is their total
+ *   d_out_off  nrec + 1 entries: entry i is d_out[d_out_off[i] .. d_out_off[i + 1]); d_out_off[0] = 0, d_out_off[nrec] = *out_len
+ *   d_begin, d_end   both null or both given, nrec entries each: the VIEW form, absolute positions in d_in:
+ *              d_off[i] <= d_begin[i] <= d_end[i] <= d_off[i + 1], and entry i is d_in[d_begin[i] .. d_end[i]).  They are written
+ *              before the capacity decision and are valid under TRRE_E_CAPACITY: with d_out and d_out_off null and cap == 0 they
+ *              are all that a caller of string views needs, and *out_len is still reported.
+ * d_out may be null only with cap == 0, and d_out_off only when d_out is: that is the size query.  When no entry has bytes the
+ * call returns TRRE_OK and writes the offsets (all zero; if d_out_off is not null) and the ranges.  nrec == 0 is valid with
+ * n == 0: TRRE_OK, and d_out_off[0] = 0 if d_out_off is not null.  The offsets' check (TRRE_E_ARG, nothing written), a string that
+ * holds a '\n' (TRRE_E_ARG, found on the device before anything of the caller's is written) and a split-form scan in flight: as
+ * for trre_field_device_strings.  Refused before the device is touched, in this order: a null argument, only one of d_begin and
+ * d_end among them; flags == 0 or a bit other than the two defined; a program compiled with TRRE_MODE_SUB; any other program not
+ * compiled with TRRE_MODE_SPANS (all TRRE_E_ARG); TRRE_KERNEL_BACKTRACK forced through trre_set_kernel (TRRE_E_UNSUPPORTED);
+ * 2^55 strings or bytes; d_out overlapping d_in — there is no in-place form; any other overlap among d_in, d_out, d_off,
+ * d_out_off, d_begin and d_end (all TRRE_E_ARG).
+ *   TRRE_E_CAPACITY  exactly when *out_len > cap: *out_len, d_begin and d_end are valid; d_out and d_out_off have not been
+ *                    written at all, and a retry with that room succeeds.
+ *   TRRE_E_DIVERGES  *out_len = 0; the arrays are unspecified; trre_last_error() holds the reference's message.
+ * How: the span call's passes with its list offsets L, and nothing else of it, stored into an array of the library's own.  One
+ * more pass over the framed text, the span call's emit pass with other stores: the markers of match r of a string's c matches
+ * park their positions when r is 0 (the left side), c - 1 or c - 2 (the right side) — six words per string at the most, each
+ * stored by one lane, the test on ranks alone.  One pass over the strings, 64 to a wave, applies the rule above to the parked
+ * words that exist and stores every string's range, into d_begin and d_end too.  Then the field call's passes, unchanged, with
+ * those ranges and k = 0 over 16 KiB tiles of the INPUT: the entries and their bytes per tile, their two exclusive sums, whose
+ * totals are nrec and *out_len, read back in one synchronisation; and its compaction pass, which writes the tile's contiguous
+ * part of d_out as whole aligned 16-byte vectors.  Every byte and word is stored once.
+ * Device memory, kept by the (prog, device) until trre_free: the field call's, and 48 nrec bytes of parked words.  Synchronous
+ * with respect to `stream`; trre_last_scan_flags as for the strings call. */
+#define TRRE_TRIM_LEFT  1u   /* remove the match that starts at the string's start */
+#define TRRE_TRIM_RIGHT 2u   /* remove the match that ends at the string's end */
+int trre_trim_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint32_t flags,
+                             uint8_t* d_out, size_t cap, int64_t* d_out_off, int64_t* d_begin, int64_t* d_end,
+                             size_t* out_len, void* stream);
 
 /* Replaced strings: the same column of strings under a program compiled with TRRE_MODE_SUB, with SOME of every string's matches
  * replaced by what they print — sed 's/x/y/' (the first match only), re.sub(p, r, s, count), s.str.replace(p, r, n=1), SQL's

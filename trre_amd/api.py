@@ -37,6 +37,8 @@ E_DEVICE, E_ARG, E_DIVERGES, E_CAPACITY = -6, -7, -8, -9
 
 FILTER_INVERT = 1
 SPLIT_FROM_END = 1
+TRIM_LEFT, TRIM_RIGHT = 1, 2
+_TRIM_SIDES = {"left": TRIM_LEFT, "right": TRIM_RIGHT, "both": TRIM_LEFT | TRIM_RIGHT}
 
 
 class TrreError(RuntimeError):
@@ -108,6 +110,7 @@ def lib():
                                                  ctypes.POINTER(sz), vp]
         L.trre_fieldn_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32, vp, sz, vp, vp,
                                                  ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+        L.trre_trim_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, vp, vp, ctypes.POINTER(sz), vp]
         L.trre_sub_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, ctypes.c_int64, vp, sz, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_nth_device_strings.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
         L.trre_scan_enqueue.argtypes = [vp, vp, sz, vp, sz, vp]
@@ -604,6 +607,55 @@ class Program:
         recs, off, values, offsets = _pack(records, device)
         out, out_off, valid = self.field_strings(values, offsets, k, limit=limit, from_end=from_end)
         return [b if ok else None for b, ok in zip(_read_back(out, out_off), valid.cpu().numpy().tolist())]
+
+    def _trim_call(self, values, offsets, side, stream):
+        """trre_trim_device_strings on a column: (call(d_out, cap, d_out_off, d_begin, d_end) -> rc, *out_len, nrec)"""
+        if side not in _TRIM_SIDES:
+            raise ValueError("side must be 'left', 'right' or 'both', not %r" % (side,))
+        flags = _TRIM_SIDES[side]
+        n, nrec, s = _column(values, offsets, stream)
+        m = ctypes.c_size_t()
+
+        def call(o, cap, oo, begin, end):
+            return lib().trre_trim_device_strings(self._h, values.data_ptr() if n else None, n, offsets.data_ptr(), nrec, flags, o, cap, oo,
+                                                  begin, end, ctypes.byref(m), s)
+        return call, m, nrec
+
+    def trim_strings(self, values, offsets, side="both", stream=None):
+        """Trimmed strings (trre_trim_device_strings; a program compiled with mode="spans"): values and offsets as for
+        scan_strings, no string holding a b"\\n".  Every string loses the match that starts at its start (side="left":
+        s.str.lstrip, removeprefix), the match that ends at its end (side="right": rstrip, removesuffix) or both (side="both":
+        strip, SQL's TRIM, re.sub('^P|P$', '', s)); one match a side, so strip() of a class is the pattern [class]+.  Returns
+        (out, out_offsets): string i's entry is out[out_offsets[i]:out_offsets[i + 1]].  Two calls: the size query, then the one
+        that fills a buffer of exactly that size."""
+        import torch
+        call, m, nrec = self._trim_call(values, offsets, side, stream)
+
+        def alloc(m):
+            out = torch.empty(m + 16, dtype=torch.uint8, device=values.device)
+            out_off = torch.zeros(nrec + 1, dtype=torch.int64, device=values.device)     # (no entry has bytes: all zero, as they are)
+            return (out[:m], out_off), (out.data_ptr(), m, out_off.data_ptr(), None, None)
+        return _query_then_fill(call, (None, 0, None, None, None), alloc, (m,), values.device)
+
+    def trim_ranges(self, values, offsets, side="both", stream=None):
+        """The view form of trim_strings: (begin, end), int64, nrec entries each — string i's entry is values[begin[i]:end[i]],
+        positions in values, absolute.  One call without output: nothing is copied."""
+        import torch
+        call, _, nrec = self._trim_call(values, offsets, side, stream)
+        begin = torch.empty(nrec, dtype=torch.int64, device=values.device)
+        end = torch.empty(nrec, dtype=torch.int64, device=values.device)
+        with torch.cuda.device(values.device):
+            rc = call(None, 0, None, begin.data_ptr(), end.data_ptr())
+        if rc not in (0, E_CAPACITY):
+            _check(rc)
+        return begin, end
+
+    def trim_list(self, records, side="both", device=0):
+        """list of bytes in -> list of bytes out: every string trimmed (through trim_strings)"""
+        if side not in _TRIM_SIDES:
+            raise ValueError("side must be 'left', 'right' or 'both', not %r" % (side,))
+        recs, off, values, offsets = _pack(records, device)
+        return _read_back(*self.trim_strings(values, offsets, side))
 
     def sub_strings(self, values, offsets, count=-1, first=0, stream=None):
         """Some of every string's matches replaced by what they print (trre_sub_device_strings; a program compiled with

@@ -1110,6 +1110,67 @@ int trre_fieldn_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, cons
                      static_cast<hipStream_t>(stream));
 }
 
+// every string without the match at its start and the match at its end: steps 1 - 6 are the filter call's; 7 the words the
+// markers of every string's first and last two matches park, and the bounds from them — the ranges, also into the caller's d_begin
+// and d_end, before the capacity decision; 8 and 9 the field call's count and emit passes with k = 0: every string has its entry
+static int trim_on(trre_prog* p, DeviceState* st, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint32_t flags, uint8_t* d_out,
+                   size_t cap, int64_t* d_out_off, int64_t* d_begin, int64_t* d_end, size_t* out_len, hipStream_t s) {
+    using namespace trre;
+    ScanCtx* cx = &st->ctx;
+    SpanMarks mk;
+    int rc = span_marks(p, st, d_in, n, d_off, nrec, false, s, &mk);
+    if (rc) return rc;
+    if (mk.empty) {
+        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return TRRE_OK;
+    }
+    HIP_TRY(cx->d_field_bounds.reserve(nrec, 2 * nrec * 8));
+    HIP_TRY(cx->d_trim_marks.reserve(nrec, 6 * nrec * 8));
+    TrimArgs t{};
+    t.flags = flags; t.marks = cx->d_trim_marks; t.begin = d_begin; t.end = d_end;
+    FieldArgs& a = t.a;
+    a.k = 0; a.lo = cx->d_field_bounds; a.hi = a.lo + nrec;
+    rc = filter_tiles(cx, mk.pa, d_in, n, d_off, nrec, s, &a.f, [&](const SpanArgs& pa) { launch_trim_bounds(pa, t, s); });
+    if (rc) return rc;
+    launch_field_count(a, s);
+    uint64_t tot[2] = {0, 0};
+    rc = scan_counts(a.f.cnt, a.f.base, 2, a.f.tiles, s, tot);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (tot[0] != nrec || tot[1] > n) return fail(TRRE_E_DEVICE, "error: the trimmed strings do not add up (internal)");
+    const size_t bytes = (size_t)tot[1];
+    if (out_len) *out_len = bytes;
+    if (bytes > cap) return fail(TRRE_E_CAPACITY, "error: output buffer too small");
+    if (d_out_off) {
+        a.f.out = d_out; a.f.out_len = (int64_t)bytes; a.f.out_off = d_out_off;
+        launch_field_emit(a, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return TRRE_OK;
+}
+
+int trre_trim_device_strings(trre_prog* p, const uint8_t* d_in, size_t n, const int64_t* d_off, size_t nrec, uint32_t flags, uint8_t* d_out, size_t cap,
+                             int64_t* d_out_off, int64_t* d_begin, int64_t* d_end, size_t* out_len, void* stream) {
+    g_scan_flags = 0;
+    if (out_len) *out_len = 0;
+    if (!p || !d_off || (n && !d_in) || (cap && !d_out) || (!d_out_off && (d_out || cap)) || (!d_begin != !d_end))
+        return fail(TRRE_E_ARG, "error: null argument");
+    if (!flags || (flags & ~(TRRE_TRIM_LEFT | TRRE_TRIM_RIGHT)))
+        return fail(TRRE_E_ARG, "error: flags must be TRRE_TRIM_LEFT, TRRE_TRIM_RIGHT or both");
+    if (int rc = spans_program(p, "trimmed strings")) return rc;
+    if (nrec >= ((size_t)1 << 55) || n >= ((size_t)1 << 55)) return fail(TRRE_E_ARG, "error: too many records or bytes");
+    const size_t ob = (nrec + 1) * 8, pb = d_out_off ? ob : 0, rb = d_begin ? nrec * 8 : 0, cb = d_out ? cap : 0;
+    if (ranges_overlap(d_in, n, d_out, cb)) return fail(TRRE_E_ARG, "error: the output overlaps the input (the trimmed strings are not made in place)");
+    if (any_overlap({{d_in, n}, {d_out, cb}}, {{d_off, ob}, {d_out_off, pb}, {d_begin, rb}, {d_end, rb}}))
+        return fail(TRRE_E_ARG, "error: an offsets array overlaps the data or another offsets array");
+    ColumnCall c;
+    if (const int rc = c.begin(p)) return rc;
+    return trim_on(p, c.st, d_in, n, d_off, nrec, flags, d_out, cap, d_out_off, d_begin, d_end, out_len, static_cast<hipStream_t>(stream));
+}
+
 // ---- replaced strings (records_block.hpp) -----------------------------------------------------------------------------------
 // Steps 1 - 5 are the span call's, 6 its emit pass into the library's own arrays, 7 the find call's texts scan of the same staged
 // text under the inner program (stt: its state; its context holds the framed texts).  The outer context holds everything else.

@@ -20,6 +20,7 @@ struct FilterArgs;
 struct FieldArgs;
 struct SplitnArgs;
 struct FieldnArgs;
+struct TrimArgs;
 struct SubArgs;
 struct NthArgs;
 
@@ -144,6 +145,10 @@ void launch_splitn_emit(const SplitnArgs& a, void* stream);
 // launch_field_emit(a.a)
 void launch_fieldn_bounds(const SpanArgs& sp, const FieldnArgs& a, void* stream);
 void launch_fieldn_count(const FieldnArgs& a, void* stream);
+// trimmed strings (records_block.hpp), behind launch_span_emit's list offsets: the words the markers of every string's first and
+// last two matches park (a.marks; sp: the span call's tiles of the framed text), then every string's bounds from them (a.a.lo,
+// a.a.hi, a.begin, a.end); the count and emit passes are launch_field_count(a.a) and launch_field_emit(a.a)
+void launch_trim_bounds(const SpanArgs& sp, const TrimArgs& a, void* stream);
 // replaced strings (records_block.hpp), behind launch_span_emit's spans and list offsets and launch_find_unframe's texts: the
 // selection bits and the selected matches, texts' bytes and matched bytes per chunk of sub_chunk_matches() matches (a.cnt; a.status
 // |= 1 when the arrays are out of order); then — behind their three exclusive scans — where every segment starts; the output

@@ -1380,6 +1380,68 @@ TRRE_HD void fieldn_count_strings(const FieldnArgs& a, const FilterTile<G>& t, i
     if (tid == 0 && t.i1 < a.a.f.nrec) bytes += field_clip(a.a, t.i1, t.t0, t.t1);
 }
 
+// ---- trimmed strings (trre_trim_device_strings) -----------------------------------------------------------------------------
+// Every string without the match that touches its start and the match that touches its end: str.strip / lstrip / rstrip, SQL's
+// TRIM, removeprefix / removesuffix.  String i = [off[i], off[i + 1]) of len bytes has the spans (s_0, e_0) .. (s_{c-1}, e_{c-1}):
+//     lo = max{ e_j : s_j == 0 }    (the left side asked for; else, and with no such match, 0)
+//     hi = min{ s_j : e_j == len }  (the right side asked for; else, and with no such match, len)
+// and the entry is [lo, max(lo, hi)).  At most one match starts at 0 (an attempt at a position yields one match), and it is
+// match 0; at most two end at len, a non-empty one and the empty tail attempt behind it ('x*' on "xxbxx": (3, 5) and (5, 5), the
+// trim is "b"), and they are matches c - 1 and c - 2.  So six words per string decide both bounds: where matches 0, c - 1 and
+// c - 2 start and end.  The entry is one contiguous range inside its string, so the output is the field call's compaction with
+// k = 0 (every string has its entry).  The passes, behind k_span_emit's list offsets L in an array of the library's own:
+//   k_trim_pick     k_span_emit's mark images, scans and ranks over the framed tiles; the A (the B) of match r of its string's c
+//                   parks its position in the word of every role the match plays: match 0 (the left side), match c - 1 and
+//                   match c - 2 (the right side).  The test is on ranks alone: L twice per marker; a '\n' lane stores nothing
+//   k_trim_bounds   over the strings, 64 to a wave: the rule above from off, L and the parked words that exist (none for c = 0,
+//                   the words of c - 2 for c >= 2 only); lo_i and hi_i = max(lo_i, hi_i) into the field call's bounds, and into
+//                   the caller's begin and end where given
+//   k_filter_part, k_field_count, k_chunk_scan twice, k_field_emit   the field call's, unchanged, with k = 0
+// Who writes which word: every parked word the one marker lane whose match plays the word's role in its string (a match that
+// plays two roles — the only match of its string is match 0 and match c - 1 — parks twice, into two words); lo_i, hi_i, begin[i]
+// and end[i] the lane of k_trim_bounds that owns string i.  A side that is not asked for parks nothing and reads nothing.
+constexpr uint32_t kTrimLeft = 1u, kTrimRight = 2u;   // TRRE_TRIM_LEFT, TRRE_TRIM_RIGHT
+
+struct TrimArgs {
+    FieldArgs a;            // as the field call has them, k = 0; valid and words are not used
+    uint32_t flags;
+    int64_t* marks;         // [6][nrec] where match 0 starts and ends, match c - 1, match c - 2: positions in d_in
+    int64_t* begin;         // [nrec] the caller's, or null: lo_i
+    int64_t* end;           // [nrec] ... hi_i
+};
+
+// k_trim_pick, behind the barrier that completes bits and pv: the words the tile's markers park
+template <class G>
+TRRE_HD void trim_pick_markers(const TrimArgs& a, const SpanArgs& sp, int64_t b, int tid, const uint16_t* bits, const uint32_t* pv_ab,
+                               const uint32_t* pv_nl) {
+    span_each_marker<G>(sp, b, tid, bits, pv_ab, pv_nl, [&](int kind, int64_t na, int64_t nb, int64_t nl, int64_t pos) {
+        if (kind == 2 || nl >= a.a.f.nrec) return;        // (never beyond: the newline total was checked against nrec before)
+        const int64_t l0 = a.a.f.loff[nl], c = a.a.f.loff[nl + 1] - l0, r = (kind == 0 ? na : nb) - l0;
+        int64_t* w = a.marks + kind * a.a.f.nrec + nl;    // (the A's word; the B's is nrec behind it)
+        if ((a.flags & kTrimLeft) && r == 0) w[0] = pos;
+        if (a.flags & kTrimRight) {
+            if (r == c - 1) w[2 * a.a.f.nrec] = pos;
+            if (r == c - 2) w[4 * a.a.f.nrec] = pos;
+        }
+    });
+}
+// k_trim_bounds, one lane: string i's bounds by the rule, from the parked words that exist
+TRRE_HD void trim_bounds(const TrimArgs& a, int64_t i) {
+    const int64_t nrec = a.a.f.nrec, s = a.a.f.off[i], e = a.a.f.off[i + 1], c = a.a.f.loff[i + 1] - a.a.f.loff[i];
+    const int64_t* w = a.marks + i;
+    int64_t lo = s, hi = e;
+    if (c >= 1) {
+        if ((a.flags & kTrimLeft) && w[0] == s) lo = w[nrec];
+        if ((a.flags & kTrimRight) && w[3 * nrec] == e) {
+            hi = w[2 * nrec];
+            if (c >= 2 && w[5 * nrec] == e && w[4 * nrec] < hi) hi = w[4 * nrec];
+        }
+    }
+    if (hi < lo) hi = lo;
+    a.a.lo[i] = lo; a.a.hi[i] = hi;
+    if (a.begin) { a.begin[i] = lo; a.end[i] = hi; }
+}
+
 // ---- replaced strings (trre_sub_device_strings) ----------------------------------------------------------------------------
 // Some of every string's matches replaced by what they print: a splice of two sources the library already has.  The span call's
 // emit pass leaves, in arrays of the library's own, S[j], E[j] (where match j of the column starts and ends in d_in) and the list

@@ -104,6 +104,7 @@ struct ScanCtx {
     DevBuf<uint8_t> d_find_marks;     // ... the marks scan unframed: a byte per match (bytes)
     DevBuf<int64_t> d_filter_lists;   // trre_filter_device_strings, trre_field_device_strings, trre_sub_device_strings: the span call's list offsets [nrec + 1] (entries)
     DevBuf<int64_t> d_field_bounds;   // trre_field_device_strings: where every string's field starts [nrec], then where it ends [nrec] (strings)
+    DevBuf<int64_t> d_trim_marks;     // trre_trim_device_strings: where every string's matches 0, c - 1 and c - 2 start and end [6][nrec] (strings)
     DevBuf<uint64_t> d_splitn_cnt;    // trre_splitn_device_strings: cnt [2][tiles], base [2][tiles + 1]: kept bytes, cutting matches per framed tile (tiles)
     DevBuf<int64_t> d_sub_idx;        // trre_sub_device_strings: S, E, XO, P, each [found + 2] with entry -1 in front (matches)
     DevBuf<uint8_t> d_sub_texts;      // ... the texts scan unframed (bytes)

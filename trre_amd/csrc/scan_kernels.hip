@@ -2047,6 +2047,23 @@ __global__ __launch_bounds__(FG::THREADS) void k_fieldn_count(FieldnArgs a) {
     tile_totals<uint64_t>(c, a.a.f.cnt, a.a.f.tiles, blockIdx.x);
 }
 
+// ---- trimmed strings (records_block.hpp; column_calls.cpp: trre_trim_device_strings) --------------------------------------
+// The words the markers park: k_span_emit's marks, scans and barriers (span_tile_marks) with trim_pick_markers' stores.
+__global__ __launch_bounds__(SG::THREADS) void k_trim_pick(SpanArgs sp, TrimArgs a) {
+    span_tile_marks(sp, [&](int64_t b, int tid, const uint16_t* bits, const uint32_t* pv_ab, const uint32_t* pv_nl) {
+        trim_pick_markers<SG>(a, sp, b, tid, bits, pv_ab, pv_nl);
+    });
+}
+
+// Every string's bounds from the offsets, the list offsets and the parked words.  A workgroup takes groups of kMatchThreads
+// consecutive strings in turn, a wave 64 of them (k_field_init's shape).  No LDS, no ballot: nothing is shared between lanes.
+__global__ __launch_bounds__(kMatchThreads) void k_trim_bounds(TrimArgs a, int64_t groups) {
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const int64_t i = g * kMatchThreads + threadIdx.x;
+        if (i < a.a.f.nrec) trim_bounds(a, i);
+    }
+}
+
 // ---- replaced strings (records_block.hpp; runtime.cpp: trre_sub_device_strings) --------------------------------------------
 // The selection bits and the chunk's three sums; a chunk out of order sets the status word.  No LDS but tile_totals' own.
 __global__ __launch_bounds__(FG::THREADS) void k_sub_plan(SubArgs a) {
@@ -2224,6 +2241,13 @@ void launch_fieldn_count(const FieldnArgs& a, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_filter_part, dim3((unsigned)((a.a.f.tiles + 1 + 255) / 256)), dim3(256), 0, s, a.a.f);
     hipLaunchKernelGGL(k_fieldn_count, dim3((unsigned)a.a.f.tiles), dim3(FG::THREADS), 0, s, a);
+}
+
+void launch_trim_bounds(const SpanArgs& sp, const TrimArgs& a, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t groups = (a.a.f.nrec + kMatchThreads - 1) / kMatchThreads;
+    hipLaunchKernelGGL(k_trim_pick, dim3((unsigned)sp.tiles), dim3(SG::THREADS), 0, s, sp, a);
+    hipLaunchKernelGGL(k_trim_bounds, dim3((unsigned)(groups < 1 ? 1 : groups > 256 * 16 ? 256 * 16 : groups)), dim3(kMatchThreads), 0, s, a, groups);
 }
 
 void launch_span_count(const SpanArgs& a, void* stream) {
